@@ -2,6 +2,12 @@
 """Training-throughput benchmark of the SASRec / BERT4Rec HIP hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warmup steps, times the K steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the result line.  --full adds the legs that take runs of their own: the
+in-kernel stamps of the dominant launch inside the timed steps, its event-timed and isolated re-timing (roofline)
+and the CPU baseline; without it the line's roofline and cpu_baseline are null.
 
 BASELINE.json's metric is training sequences/sec for SASRec T=200 d=128 (configs[1] = cfg2,
 the default).  For N > 1 one process runs per GPU: either the driver's torchrun starts them
@@ -13,7 +19,7 @@ scaling (B sequences per GPU).
 One "step" = zero_grad + forward + loss + backward (+ all-reduce) + Adam on one synthetic batch
 already resident in HBM: the step is captured once in HIP graphs and replayed; each replay first
 copies its batch into the graph's static input buffers (device to device).  Rank 0 prints ONE
-JSON line with metric/value/unit/... plus
+JSON line with metric/value/unit/... plus, under --full,
   roofline     -- the dominant kernel (most device time per step, from the rocprof profile
                   committed under profiles/), re-timed here with HIP events on its own stream,
                   algorithmic bytes or flops per launch / average launch time vs the chip peak;
@@ -83,6 +89,13 @@ def parse():
     ap.add_argument("--sampler", default="host", choices=["host", "device"],
                     help="SAS: 'device' = batches drawn each step by the on-device WarpSampler "
                          "(rs_sas_sample) inside the step's graph, from synthetic user histories")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel stamps in the timed steps, the "
+                         "dominant kernel's roofline (--roofline-replays) and the CPU baseline "
+                         "(--cpu-baseline-seconds); off: those two options are unused and the line holds null for both")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): loss.npy "
+                         "and one param.<state-dict key>.npy per parameter (see dump_outputs)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -392,6 +405,36 @@ def cpu_baseline(cfg, B, seconds):
             "cpu_share": share}
 
 
+# ------------------------------------------------------------------------------------ outputs
+DUMP_BUDGET = 12 * 2 ** 20       # float32 elements over all param.*.npy files: 48 MiB of the 64 MB a dump may take
+
+
+def dump_outputs(path, loss, state):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float32 .npy files.
+    loss.npy: the losses the last replay returned (one per step unrolled into it, the last entry = the last timed
+    step's).  param.<key>.npy: every state-dict entry as that step's Adam update left it (the fp32 masters).  When
+    the entries together exceed DUMP_BUDGET elements (the BERT item tables), the small entries stay whole and each
+    entry larger than an equal share of what they leave of the budget is written as a fixed sample instead: its
+    flattened values at sorted indices drawn from default_rng(0), in key order -- the same indices in every run of
+    the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    cap, left = None, DUMP_BUDGET
+    sizes = sorted(v.numel() for v in state.values())
+    for i, n in enumerate(sizes):
+        if n > left // (len(sizes) - i):
+            cap = max(1, left // (len(sizes) - i))
+            break
+        left -= n
+    rng = np.random.default_rng(0)
+    for k in sorted(state):
+        v = state[k].detach()
+        if cap is not None and v.numel() > cap:
+            idx = np.unique(rng.integers(0, v.numel(), cap))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(path, f"param.{k}.npy"), v.float().cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------ main
 def main():
     args = parse()
@@ -432,12 +475,12 @@ def main():
     vshard = cfg["model"] == "bert" and world > 1 and (
         args.vocab_shard == "on" or (args.vocab_shard == "auto" and cfg["V"] >= 100000))
     trainer = FusedTrainStep(model, lr=1e-3, max_labelled=max_lab, vocab_shard=vshard)
-    # the dominant kernel is timed live, inside every timed step: the step graph is captured with kernel
+    # --full: the dominant kernel is timed live, inside every timed step: the step graph is captured with kernel
     # stamps on (first wave in / last wave out s_memrealtime ticks of each stamped launch, per step)
     from rbm_amd import ops
     NMARK, WAVES = 8, 16384
-    sbuf = None if args.no_graph else torch.zeros(4 + args.steps * NMARK * (1 + WAVES), dtype=torch.int64,
-                                                  device="cuda")
+    sbuf = None if args.no_graph or not args.full else torch.zeros(4 + args.steps * NMARK * (1 + WAVES),
+                                                                   dtype=torch.int64, device="cuda")
     stamps = None if sbuf is None else (sbuf, (dominant(cfg),))
 
     if args.steps_per_graph == "auto":
@@ -541,6 +584,12 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = tt.item()
     final_loss = float(loss.float().reshape(-1)[-1].item())
+    if args.dump_outputs:
+        # before anything below runs further steps of this trainer; state_dict() is collective when sharded
+        state = trainer.state_dict()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss, state)
 
     live, live_expected = None, None
     if sbuf is not None:
@@ -554,7 +603,7 @@ def main():
     # so its launches then run back to back as in a replay and the events see device time only.  Every rank alike
     # (under DP the steps hold the collectives).
     event_us, ev_cost, event_raw = None, None, None
-    if not args.no_graph and args.roofline_replays > 0:
+    if args.full and not args.no_graph and args.roofline_replays > 0:
         pairs = ops.event_timing((dominant(cfg),))
         empty = []
         try:
@@ -575,13 +624,13 @@ def main():
     labelled = (sum(float((lab != 0).sum()) for _, lab in host_batches) / len(host_batches)
                 if cfg["model"] == "bert" else None)
     roof = roofline(cfg, B, args.dtype, live_us=live, labelled=labelled, live_expected=live_expected,
-                    event_us=event_us) if rank == 0 else None
+                    event_us=event_us) if rank == 0 and args.full else None
     if roof is not None and event_us:
         roof["event_pair_raw_us"] = round(event_raw, 2)
         roof["event_pair_cost_us"] = round(ev_cost, 2)
     if rank == 0:
-        cpu = cpu_baseline(cfg, B, args.cpu_baseline_seconds) if world == 1 and args.cpu_baseline_seconds > 0 \
-            else None
+        cpu = cpu_baseline(cfg, B, args.cpu_baseline_seconds) \
+            if args.full and world == 1 and args.cpu_baseline_seconds > 0 else None
         line = {
             "metric": "training sequences/sec, SASRec L=200 d=128 at 1/2/4/8 MI355X; HR@10 parity",
             "value": round(world * B * args.steps / elapsed, 1),
@@ -600,7 +649,7 @@ def main():
                        "global_batch": world * B, "per_gpu_batch": B, "seq_len": cfg["T"], "hidden": cfg["d"],
                        "blocks": cfg["L"], "heads": cfg["h"], "num_items": cfg["V"], "parallelism": f"dp{world}",
                        "hip_graph": not args.no_graph, "bench_config": args.config,
-                       "sampler": args.sampler, "steps_per_graph": S},
+                       "sampler": args.sampler, "steps_per_graph": S, "full": args.full},
             "final_loss": round(final_loss, 5),
             "roofline": roof,
             "cpu_baseline": cpu,

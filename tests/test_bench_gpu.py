@@ -18,7 +18,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 @pytest.mark.parametrize("config", ["cfg2", "cfg4"])
 def test_bench_json_line(config):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "6",
-                        "--warmup", "2", "--cpu-baseline-seconds", "0.5"], capture_output=True, text=True,
+                        "--warmup", "2", "--full", "--cpu-baseline-seconds", "0.5"], capture_output=True, text=True,
                        timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -43,7 +43,7 @@ def test_bench_ranks_gloo(n):
     the live world size, the replicas' parameters equal after the warmup steps, the whole-job value over all ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dist-backend", "gloo",
-                        "--config", "cfg2", "--steps", "4", "--warmup", "2", "--roofline-replays", "2"],
+                        "--config", "cfg2", "--steps", "4", "--warmup", "2", "--full", "--roofline-replays", "2"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -5,7 +5,7 @@ BS/trainers/bert.py:40) -- even when the ranks hold different valid counts.  The
 gradients come from the CPU oracle (the GPU kernels compute the same quantity; the single-GPU
 DP path is covered by tests/test_dp_gpu.py)."""
 import os
-import socket
+import tempfile
 
 import numpy as np
 import pytest
@@ -16,12 +16,12 @@ import torch.multiprocessing as mp
 from conftest import ROOT, load_golden
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _rendezvous(d):
+    """init_method of a file store inside the test's own directory: the ranks meet through it, so there is no port
+    that another process could take between choosing it and binding it."""
+    fd, path = tempfile.mkstemp(prefix="rdzv", dir=str(d))
+    os.close(fd)
+    return "file://" + path
 
 
 def _flat(grads, names, loss_sum, count):
@@ -29,13 +29,12 @@ def _flat(grads, names, loss_sum, count):
     return v
 
 
-def _worker(rank, world, port, kind, bucket, out_dir):
+def _worker(rank, world, rdzv, kind, bucket, out_dir):
     import sys
     sys.path.insert(0, ROOT)
     import rbm_amd  # noqa: F401
     from rbm_amd import dp
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         names, flat, _ = _local(kind, rank, world)
         dp.allreduce_grads(flat, bucket_numel=bucket)
@@ -74,8 +73,7 @@ def test_dp_two_ranks_equal_single_device(kind, bucket, tmp_path):
     sys.path.insert(0, ROOT)
     from oracle import bert as obert
     from oracle import sas as osas
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, kind, bucket, str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, _rendezvous(tmp_path), kind, bucket, str(tmp_path)), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "r0.pt", weights_only=True)
     r1 = torch.load(tmp_path / "r1.pt", weights_only=True)
     assert torch.equal(r0["g"], r1["g"])                  # replicas apply the same update
@@ -94,13 +92,12 @@ def test_dp_two_ranks_equal_single_device(kind, bucket, tmp_path):
     assert float((r0["g"] - ref).norm() / ref.norm()) < 1e-12
 
 
-def _bucket_worker(rank, world, port, out_dir):
+def _bucket_worker(rank, world, rdzv, out_dir):
     import sys
     sys.path.insert(0, ROOT)
     import rbm_amd  # noqa: F401
     from rbm_amd import dp
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         g = torch.Generator().manual_seed(rank)
         flat = torch.randn(1000, generator=g)
@@ -119,8 +116,7 @@ def _bucket_worker(rank, world, port, out_dir):
 def test_bucketed_exchange_equals_one_allreduce(tmp_path):
     """dp.BucketedExchange (the data-parallel step's all-reduce, bucket by bucket as the backward finishes them)
     sums exactly what one all-reduce of the whole buffer sums, on every rank."""
-    port = _free_port()
-    mp.spawn(_bucket_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_bucket_worker, args=(2, _rendezvous(tmp_path), str(tmp_path)), nprocs=2, join=True)
     for r in range(2):
         d = torch.load(tmp_path / f"b{r}.pt", weights_only=True)
         assert torch.equal(d["flat"], d["ref"])
@@ -145,13 +141,12 @@ def test_ranks_have_different_counts():
     _ = np
 
 
-def _shard_worker(rank, world, port, V1, out_dir):
+def _shard_worker(rank, world, rdzv, V1, out_dir):
     import sys
     sys.path.insert(0, ROOT)
     import rbm_amd  # noqa: F401
     from rbm_amd.vocab_parallel import VocabShard
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         vs = VocabShard(V1)
         full = torch.full((V1, 3), -1.0)
@@ -166,7 +161,7 @@ def _shard_worker(rank, world, port, V1, out_dir):
 def test_vocab_shard_ranges_and_gather(tmp_path, world, V1):
     """rbm_amd.vocab_parallel.VocabShard: 128-aligned disjoint shards covering [0, V1); gather_rows assembles
     the owners' rows on every rank (the checkpoint layout of the vocabulary-sharded BERT head)."""
-    mp.spawn(_shard_worker, args=(world, _free_port(), V1, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_shard_worker, args=(world, _rendezvous(tmp_path), V1, str(tmp_path)), nprocs=world, join=True)
     spans = []
     for r in range(world):
         d = torch.load(tmp_path / f"s{r}.pt", weights_only=True)
@@ -177,13 +172,12 @@ def test_vocab_shard_ranges_and_gather(tmp_path, world, V1):
     assert all(v0 % 128 == 0 for v0, _ in spans)
 
 
-def _carve_worker(rank, world, port, out_dir):
+def _carve_worker(rank, world, rdzv, out_dir):
     import sys
     sys.path.insert(0, ROOT)
     import rbm_amd  # noqa: F401
     from rbm_amd import dp
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         g = torch.Generator().manual_seed(rank)
         flat = torch.randn(1000, generator=g)
@@ -205,7 +199,7 @@ def _carve_worker(rank, world, port, out_dir):
 def test_carved_buckets_leave_the_table_region(tmp_path):
     """dp.carve + multi-range buckets (the BERT step with a sparse token-table exchange): every range but the carved
     one is all-reduced exactly as one dense all-reduce sums it; the carved region keeps this rank's values."""
-    mp.spawn(_carve_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_carve_worker, args=(2, _rendezvous(tmp_path), str(tmp_path)), nprocs=2, join=True)
     for r in range(2):
         d = torch.load(tmp_path / f"c{r}.pt", weights_only=True)
         out = torch.ones(1000, dtype=torch.bool)
@@ -227,14 +221,13 @@ def test_sparse_exchange_sizing():
     assert cap * d * 4 == 104_857_600 and rows * d * 4 == 1_024_002_048
 
 
-def _rows_worker(rank, world, port, out_dir):
+def _rows_worker(rank, world, rdzv, out_dir):
     import sys
     sys.path.insert(0, ROOT)
     import rbm_amd  # noqa: F401
     from rbm_amd import dp
     from rbm_amd.flat import FlatParams
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         torch.manual_seed(0)
         mod = torch.nn.Module()
@@ -273,7 +266,7 @@ def test_sharded_rows_scatter_gather(tmp_path, world):
     """dp.ShardedRows (the sharded item-table optimizer of the SAS DP step): equal 64-aligned parts tile the sharded
     region; after the exchange each rank's part holds the global gradient sum and the dense ranges (the table's tail
     included) the all-reduced values; zero_foreign clears the rest; gather assembles the owners' parts everywhere."""
-    mp.spawn(_rows_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_rows_worker, args=(world, _rendezvous(tmp_path), str(tmp_path)), nprocs=world, join=True)
     parts = []
     for r in range(world):
         d = torch.load(tmp_path / f"w{r}.pt", weights_only=True)

@@ -11,7 +11,7 @@ the backward finishes them) and as one all-reduce after it.  Each mode must
 """
 import argparse
 import os
-import socket
+import tempfile
 
 import numpy as np
 import pytest
@@ -27,12 +27,12 @@ V, T, BR, STEPS = 500, 50, 6, 3
 MODES = [(False, False), (False, True), (True, False), (True, True)]     # (graph, overlap)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _rendezvous(d):
+    """init_method of a file store inside the test's own directory: the ranks meet through it, so there is no port
+    that another process could take between choosing it and binding it."""
+    fd, path = tempfile.mkstemp(prefix="rdzv", dir=str(d))
+    os.close(fd)
+    return "file://" + path
 
 
 def _model(kind, dtype, l2=0.01):
@@ -69,12 +69,11 @@ def _reset(tr, sd):
     tr.opt.state.zero_()
 
 
-def _worker(rank, world, port, kind, dtype, out_dir, shard="off", l2=0.01):
+def _worker(rank, world, rdzv, kind, dtype, out_dir, shard="off", l2=0.01):
     import sys
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         from rbm_amd import dp as dpx
         from rbm_amd.train_step import FusedTrainStep
@@ -132,7 +131,7 @@ def _update_err(kind, k, a, ref, init):
 @pytest.mark.parametrize("kind,dtype", [("sas", "bf16"), ("sas", "fp32"), ("bert", "bf16")])
 def test_two_rank_step_equals_single_process(tmp_path, kind, dtype):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), kind, dtype, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, _rendezvous(tmp_path), kind, dtype, str(tmp_path)), nprocs=world, join=True)
     from rbm_amd.train_step import FusedTrainStep
     batches = _batches(kind, world)
     m = _model(kind, dtype)
@@ -180,12 +179,11 @@ def test_two_rank_step_equals_single_process(tmp_path, kind, dtype):
 # (BS/trainers/sas.py:49, BS/trainers/bert.py:40; BS/trainers/base.py:32-34 for the data-parallel wrapper).
 
 
-def _grad_worker(rank, world, port, kind, dtype, overlap, out_dir):
+def _grad_worker(rank, world, rdzv, kind, dtype, overlap, out_dir):
     import sys
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         from rbm_amd import dp as dpx
         from rbm_amd.train_step import FusedTrainStep
@@ -225,7 +223,8 @@ def test_multi_rank_gradient_equals_oracle(tmp_path, kind, dtype, overlap, world
     = the scaling run's rank count on the benchmarked path): with more than two ranks the all-reduce's summation order
     is no longer a + b, and every rank must still hold the same bits."""
     from conftest import check_bf16_grads, rel
-    mp.spawn(_grad_worker, args=(world, _free_port(), kind, dtype, overlap, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_grad_worker, args=(world, _rendezvous(tmp_path), kind, dtype, overlap, str(tmp_path)), nprocs=world,
+             join=True)
     rs = [torch.load(tmp_path / f"g{r}.pt", weights_only=True) for r in range(world)]
     r0 = rs[0]
     b = _batches(kind, world)[0]
@@ -298,7 +297,7 @@ def test_two_rank_sharded_item_table(tmp_path, dtype):
     for shard in ("on", "off"):
         d = tmp_path / shard
         d.mkdir()
-        mp.spawn(_worker, args=(world, _free_port(), "sas", dtype, str(d), shard, 0.0), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, _rendezvous(d), "sas", dtype, str(d), shard, 0.0), nprocs=world, join=True)
         runs[shard] = [torch.load(d / f"r{r}.pt", weights_only=True) for r in range(world)]
     on, off = runs["on"], runs["off"]
     for mode in on[0]:
@@ -341,7 +340,8 @@ def test_three_rank_sharded_item_table_equals_oracle(tmp_path):
     single-device steps on the concatenated batch (oracle float64 loss and gradients + AdamOracle) at the bars of the
     two-rank test."""
     world = 3
-    mp.spawn(_worker, args=(world, _free_port(), "sas", "fp32", str(tmp_path), "on", 0.0), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, _rendezvous(tmp_path), "sas", "fp32", str(tmp_path), "on", 0.0), nprocs=world,
+             join=True)
     rs = [torch.load(tmp_path / f"r{r}.pt", weights_only=True) for r in range(world)]
     for mode in rs[0]:
         assert all(r[mode]["equal"] for r in rs), mode

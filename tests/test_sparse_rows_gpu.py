@@ -4,7 +4,7 @@ gloo moving the tensors (the product uses RCCL) -- whose parameters after three 
 ranks exchanging the dense table (two ranks: every element is a + b either way)."""
 import argparse
 import os
-import socket
+import tempfile
 
 import numpy as np
 import pytest
@@ -50,12 +50,12 @@ def test_touched_rows_pack_unpack():
 V, T, D, BR = 20000, 50, 64, 4      # items, max_len, hidden, sequences per rank (2*200 ids << 20,002 rows)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _rendezvous(d):
+    """init_method of a file store inside the test's own directory: the ranks meet through it, so there is no port
+    that another process could take between choosing it and binding it."""
+    fd, path = tempfile.mkstemp(prefix="rdzv", dir=str(d))
+    os.close(fd)
+    return "file://" + path
 
 
 def _model():
@@ -67,12 +67,11 @@ def _model():
     return model_factory(a)
 
 
-def _worker(rank, world, port, graph, mode, out_dir):
+def _worker(rank, world, rdzv, graph, mode, out_dir):
     import sys
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         import rbm_amd.data as synth
         from rbm_amd.train_step import FusedTrainStep
@@ -100,7 +99,7 @@ def _worker(rank, world, port, graph, mode, out_dir):
 def test_sparse_token_exchange_equals_dense(tmp_path, graph):
     world = 2
     for mode in ("on", "off"):
-        mp.spawn(_worker, args=(world, _free_port(), graph, mode, str(tmp_path)), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, _rendezvous(tmp_path), graph, mode, str(tmp_path)), nprocs=world, join=True)
     for r in range(world):
         a = torch.load(tmp_path / f"on_r{r}.pt", weights_only=True)
         b = torch.load(tmp_path / f"off_r{r}.pt", weights_only=True)

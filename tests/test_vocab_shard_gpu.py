@@ -4,7 +4,7 @@ own half of out.weight / out.bias.  Their losses and, after the shards are gathe
 single-process step on the concatenated batch (bf16 tolerance: the shard kernels sum in a different order)."""
 import argparse
 import os
-import socket
+import tempfile
 
 import numpy as np
 import pytest
@@ -19,12 +19,12 @@ pytestmark = pytest.mark.gpu
 V, T, D, BR = 3000, 50, 64, 6      # items, max_len, hidden, sequences per rank
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _rendezvous(d):
+    """init_method of a file store inside the test's own directory: the ranks meet through it, so there is no port
+    that another process could take between choosing it and binding it."""
+    fd, path = tempfile.mkstemp(prefix="rdzv", dir=str(d))
+    os.close(fd)
+    return "file://" + path
 
 
 def _model(V=V):
@@ -42,12 +42,11 @@ def _batches(world, steps, V=V):
     return [[synth.bert_batch(rng, BR, T, V, mask_prob=0.3) for _ in range(world)] for _ in range(steps)]
 
 
-def _worker(rank, world, port, graph, out_dir):
+def _worker(rank, world, rdzv, graph, out_dir):
     import sys
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         from rbm_amd.train_step import FusedTrainStep
         m = _model()
@@ -74,7 +73,7 @@ def _worker(rank, world, port, graph, out_dir):
 @pytest.mark.parametrize("graph", [False, True])
 def test_vocab_sharded_head_equals_single_process(tmp_path, graph):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), graph, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, _rendezvous(tmp_path), graph, str(tmp_path)), nprocs=world, join=True)
     from rbm_amd.train_step import FusedTrainStep
     m = _model()
     tr = FusedTrainStep(m, lr=1e-3, max_labelled=world * BR * T)
@@ -105,12 +104,11 @@ def test_vocab_sharded_head_equals_single_process(tmp_path, graph):
 VB = 100_000
 
 
-def _grad_worker(rank, world, port, out_dir):
+def _grad_worker(rank, world, rdzv, out_dir):
     import sys
     sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
     try:
         from rbm_amd.train_step import FusedTrainStep
         m = _model(VB)
@@ -134,7 +132,7 @@ def test_vocab_sharded_gradient_equals_oracle(tmp_path):
     (test_bert.py: 3e-2 loss / per tensor); the attention key bias (analytically zero) against the gradient scale."""
     from oracle import bert as obert
     world = 2
-    mp.spawn(_grad_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_grad_worker, args=(world, _rendezvous(tmp_path), str(tmp_path)), nprocs=world, join=True)
     r = [torch.load(tmp_path / f"g{i}.pt", weights_only=True) for i in range(world)]
     assert (r[0]["v0"], r[0]["v1"], r[1]["v0"], r[1]["v1"]) == (0, 50048, 50048, VB + 1)
     assert r[0]["loss"] == r[1]["loss"] and r[0]["count"] == r[1]["count"]

@@ -42,7 +42,7 @@ tests() {
 bench() {
   for c in "$@"; do
     local st=""; [ "$c" = "cfg5" ] && st="--steps 30 --warmup 5"
-    timeout -k 10 900 python bench.py --config "$c" $st ${BENCH_ARGS:-} > "$OUT/bench_$c.log" 2>&1 \
+    timeout -k 10 900 python bench.py --config "$c" $st --full ${BENCH_ARGS:-} > "$OUT/bench_$c.log" 2>&1 \
       || { tail -20 "$OUT/bench_$c.log"; return 1; }
     tail -1 "$OUT/bench_$c.log" > "$OUT/bench_$c.json"
     cut -c1-200 "$OUT/bench_$c.json"
@@ -53,7 +53,7 @@ profile() {
   for c in "$@"; do
     local ps="--steps 50 --warmup 10"; [ "$c" = "cfg5" ] && ps="--steps 10 --warmup 3"
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/raw_$c" -o prof --output-format csv -- \
-      python3 bench.py --config "$c" $ps --cpu-baseline-seconds 0 ${BENCH_ARGS:-} > "$OUT/rocprof_$c.log" 2>&1 \
+      python3 bench.py --config "$c" $ps --full --cpu-baseline-seconds 0 ${BENCH_ARGS:-} > "$OUT/rocprof_$c.log" 2>&1 \
       || { tail -20 "$OUT/rocprof_$c.log"; return 1; }
     tail -1 "$OUT/rocprof_$c.log" > "$OUT/prof_bench_$c.json"
     cp "$(find "$OUT/raw_$c" -name '*kernel_stats.csv' | head -1)" "$OUT/${c}_kernel_stats.csv"
@@ -97,7 +97,7 @@ ab() {
       if [ $v = A ] && [ -n "$AENV" ]; then envs="$AENV"; elif [ $v = A ]; then envs="RS_LIB_VARIANT=${A:-a}"
       else envs="RS_AB_B=1"; fi
       env $envs timeout -k 10 300 python bench.py --config "$cfg" --steps ${STEPS:-200} --warmup 20 \
-        --cpu-baseline-seconds 0 ${BENCH_ARGS:-} > "$OUT/ab.log" 2>&1 || { tail -5 "$OUT/ab.log"; return 1; }
+        --full --cpu-baseline-seconds 0 ${BENCH_ARGS:-} > "$OUT/ab.log" 2>&1 || { tail -5 "$OUT/ab.log"; return 1; }
       echo "$v $(grep -o '"ms_per_step": [0-9.]*' "$OUT/ab.log") $(grep -o '"avg_launch_us": [0-9.]*' "$OUT/ab.log")"
     done
   done
