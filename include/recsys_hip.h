@@ -635,6 +635,37 @@ int rs_bert_mask_draws(const int64_t* user_offsets, const int64_t* user_items, i
 int rs_rank_metrics(const float* scores, const float* labels, int64_t rows, int64_t cands, int nk, const int* ks,
                     float* ws, float* out, void* stream);
 
+/* ---- full-catalogue ranking and top-K (fullrank.hip) --------------------------------------------
+ * Replaces: scoring a hand-picked candidate list and ranking it (BS/trainers/sas.py:56-62, BS/trainers/bert.py:43-52,
+ * BS/trainers/utils.py:28-57) when the candidates are EVERY item -- one vocabulary-stationary sweep, no (B, V) scores.
+ *   score      s(b, v) = fp32(sum_k h[b*ldh + k] * E[v*lde + k]) (+ bias[v] when bias != NULL); h, E in dtype
+ *              (RS_DTYPE_*), d <= 256 (any value; more: RS_ERR_UNSUPPORTED), finite scores (the caller's promise)
+ *   admissible A(b) = {v : v_lo <= v < v_hi, v not in excl[b*ldx .. + nx)}; excl int64 (nullable; nx = 0: none), each
+ *              row SORTED ascending; duplicates allowed, entries outside [v_lo, v_hi) ignored (a history's 0 padding,
+ *              BERT's [MASK] id); v_hi <= 2^31 - 256
+ *   order      v before w  <=>  s_v > s_w, or s_v == s_w and v < w
+ * rs_full_rank: rank[b] (int32) = number of v in A(b), v != target[b], before target[b]; the target itself is never
+ * excluded (the reference's negatives avoid seen items, the answer stays); a target outside [v_lo, v_hi) gives -1.
+ * target_score (nullable, fp32 [B]) = s(b, target[b]), formed by the sweep's own tile routine, so an item whose E
+ * row and bias equal the target's ties with it exactly.
+ * rs_full_topk: ids int64 [B][K], scores fp32 [B][K] = the first K of A(b) in the order; past |A(b)|: id -1, score
+ * -inf.  1 <= K <= RS_TOPK_MAX (more: RS_ERR_UNSUPPORTED).
+ * ws: rs_full_ws_bytes(dtype, B, d, v_hi - v_lo, K) bytes (host-only sizing; K = 0: rs_full_rank alone), 256-B
+ * aligned.  No allocation, no sync, graph-capturable.
+ * rs_rank_to_metrics: out[3*q + {0,1,2}] = mean over rows of [rank < k], [rank < k] / log2(rank + 2),
+ * [rank < k] / (rank + 1) for k = ks[q] (device int[nk], nk <= 8) -- Recall / NDCG / MRR@k of
+ * recalls_ndcgs_and_mrr_for_ks with one positive per row; rank -1 is a miss; ws >= 3*nk*rows floats; means in double,
+ * fixed order (as rs_rank_metrics). */
+#define RS_TOPK_MAX 128
+int64_t rs_full_ws_bytes(int dtype, int64_t B, int64_t d, int64_t nrange, int64_t K);
+int rs_full_rank(int dtype, const void* h, int64_t ldh, int64_t B, int64_t d, const void* E, int64_t lde,
+                 const float* bias, int64_t v_lo, int64_t v_hi, const int64_t* target, const int64_t* excl, int64_t nx,
+                 int64_t ldx, void* ws, int* rank, float* target_score, void* stream);
+int rs_full_topk(int dtype, const void* h, int64_t ldh, int64_t B, int64_t d, const void* E, int64_t lde,
+                 const float* bias, int64_t v_lo, int64_t v_hi, const int64_t* excl, int64_t nx, int64_t ldx, int64_t K,
+                 void* ws, int64_t* ids, float* scores, void* stream);
+int rs_rank_to_metrics(const int* rank, int64_t rows, int nk, const int* ks, float* ws, float* out, void* stream);
+
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);
 

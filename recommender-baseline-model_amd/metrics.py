@@ -38,3 +38,28 @@ def calculate_metrics(model, batch, metric_ks):
     with torch.no_grad():
         scores = model.predict(as_ids(seqs, dev), as_ids(candidates, dev))
     return recalls_ndcgs_and_mrr_for_ks(scores, torch.as_tensor(labels).to(dev), metric_ks)
+
+
+def full_rank_metrics(model, batch, metric_ks, exclude_seen=True):
+    """Exact full-rank Recall / NDCG / MRR @ k: the held-out item ranked against EVERY item of the catalogue (minus the
+    row's own history when exclude_seen; the held-out item always stays), not against 100 sampled negatives.
+    batch = (seqs, targets) -- seqs as ``predict`` takes them (BERT: ending in [MASK]), targets (B,) item ids.  The
+    same dict keys as ``recalls_ndcgs_and_mrr_for_ks``; rs_full_rank + rs_rank_to_metrics, no (B, V) scores."""
+    seqs, targets = batch
+    dev = model.engine().flat.device if hasattr(model, "engine") else next(model.parameters()).device
+    if torch.device(dev).type != "cuda":
+        raise RuntimeError("rbm_amd.metrics runs on the GPU (rs_full_rank); there is no CPU fallback")
+    ks = sorted(metric_ks, reverse=True)
+    with torch.no_grad():
+        rank = model.full_rank(as_ids(seqs, dev), as_ids(targets, dev).reshape(-1), exclude_seen)
+    ks_dev = torch.tensor(ks, dtype=torch.int32, device=dev)
+    ws = torch.empty(3 * len(ks) * rank.numel(), dtype=torch.float32, device=dev)
+    out = torch.empty(3 * len(ks), dtype=torch.float32, device=dev)
+    ops.rank_to_metrics(rank, ks_dev, ws, out)
+    v = out.cpu().tolist()
+    res = {}
+    for q, k in enumerate(ks):
+        res["Recall@%d" % k] = v[3 * q]
+        res["NDCG@%d" % k] = v[3 * q + 1]
+        res["MRR@%d" % k] = v[3 * q + 2]
+    return res

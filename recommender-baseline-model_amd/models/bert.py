@@ -57,6 +57,19 @@ class BERTModel(BaseModel):
         dev = self._flat.device
         return eng.predict(as_ids(x, dev), as_ids(candidates, dev))
 
+    @torch.no_grad()
+    def recommend(self, x, k, exclude_seen=True):
+        """(ids int64 (B, k), scores fp32 (B, k)) on the device: the k best items of the whole catalogue at the last
+        position (x ends in [MASK], as for ``predict``), best first (equal scores: lower id first), without x's own
+        items when exclude_seen; the padding id and [MASK] are never returned."""
+        return self.engine().topk(as_ids(x, self._flat.device), k, exclude_seen)
+
+    @torch.no_grad()
+    def full_rank(self, x, target, exclude_seen=True):
+        """int32 (B,) rank of target[b] among all items (0 = first), x's own items left out when exclude_seen."""
+        dev = self._flat.device
+        return self.engine().full_rank(as_ids(x, dev), as_ids(target, dev).reshape(-1), exclude_seen)
+
     def forward(self, x):
         eng = self.engine()
         ids = as_ids(x, self._flat.device)

@@ -485,6 +485,21 @@ class BERTEngine:
         h = xL.view(B, T, self.d)[:, -1, :]
         return ops.candidate_scores(h, self.W("out.weight"), cand, bias=self.Wf("out.bias"))
 
+    # full catalogue: the same hidden state against every item of [1, num_items + 1) (no padding id, no [MASK])
+    def _last_hidden(self, ids):
+        self.sync_compute_weights()
+        B, T = ids.shape
+        xL, _ = self.encode(ids, False)
+        return xL.view(B, T, self.d)[:, -1, :]
+
+    def full_rank(self, ids, target, exclude_seen=True):
+        return ops.full_rank(self._last_hidden(ids), self.W("out.weight"), target, bias=self.Wf("out.bias"), lo=1,
+                             exclude=ids if exclude_seen else None)
+
+    def topk(self, ids, k, exclude_seen=True):
+        return ops.full_topk(self._last_hidden(ids), self.W("out.weight"), k, bias=self.Wf("out.bias"), lo=1,
+                             exclude=ids if exclude_seen else None)
+
     def _n256_head(self):
         """(dE, dh) on the 256-wide-tile GEMM (gemm_n256.hip)?  bf16 and d = 256 only.  dh = dlogits E (split over
         the vocabulary) at every vocabulary size; dE = dlogits^T h from N256_MIN_V1 classes on (3.9k row tiles at

@@ -17,3 +17,9 @@ class SASModel(BaseModel):
 
     def predict(self, log_seqs, item_indices):  # for inference
         return self.sas.predict(log_seqs, item_indices)
+
+    def recommend(self, log_seqs, k, exclude_seen=True):  # top-k of the whole catalogue
+        return self.sas.recommend(log_seqs, k, exclude_seen)
+
+    def full_rank(self, log_seqs, target, exclude_seen=True):
+        return self.sas.full_rank(log_seqs, target, exclude_seen)

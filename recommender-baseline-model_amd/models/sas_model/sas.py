@@ -119,6 +119,20 @@ class SAS(nn.Module):
         dev = self._flat.device
         return eng.predict(as_ids(log_seqs, dev), as_ids(item_indices, dev))
 
+    @torch.no_grad()
+    def recommend(self, log_seqs, k, exclude_seen=True):
+        """(ids int64 (B, k), scores fp32 (B, k)) on the device: the k best items of the whole catalogue for each
+        history, best first (equal scores: lower id first), without the history's own items when exclude_seen."""
+        eng = self.engine()
+        return eng.topk(as_ids(log_seqs, self._flat.device), k, exclude_seen)
+
+    @torch.no_grad()
+    def full_rank(self, log_seqs, target, exclude_seen=True):
+        """int32 (B,) rank of target[b] among all items (0 = first), seen items left out when exclude_seen."""
+        eng = self.engine()
+        dev = self._flat.device
+        return eng.full_rank(as_ids(log_seqs, dev), as_ids(target, dev).reshape(-1), exclude_seen)
+
 
 class _SASFunction(torch.autograd.Function):
     @staticmethod
@@ -638,3 +652,14 @@ class SASEngine:
         f = self.features(ids)[:, -1, :]                    # sas.py:110 (a strided view: row stride T*d)
         # candidate scores <f_b, item_emb[c]> (sas.py:112-114): one wave per (row, candidate), rs_candidate_scores
         return ops.candidate_scores(f, self.W("item_emb.weight"), cand)
+
+    # full catalogue: the same hidden state against every item of [1, num_items + 1), no score matrix
+    def full_rank(self, ids, target, exclude_seen=True):
+        f = self.features(ids)[:, -1, :]
+        return ops.full_rank(f, self.W("item_emb.weight"), target, lo=1, hi=self.m.item_num + 1,
+                             exclude=ids if exclude_seen else None)
+
+    def topk(self, ids, k, exclude_seen=True):
+        f = self.features(ids)[:, -1, :]
+        return ops.full_topk(f, self.W("item_emb.weight"), k, lo=1, hi=self.m.item_num + 1,
+                             exclude=ids if exclude_seen else None)

@@ -797,3 +797,71 @@ def bert_mask(offsets, items, n_users, num_items, mask_prob, perm, state, salt, 
 def rank_metrics(scores, labels, ks_dev, ws, out):
     R, C = scores.shape
     call("rs_rank_metrics", ptr(scores), ptr(labels), R, C, ks_dev.numel(), ptr(ks_dev), ptr(ws), ptr(out), stream())
+
+
+# ---- full-catalogue ranking and top-K (fullrank.hip) ----------------------------------------
+RS_TOPK_MAX = 128
+
+
+def _full_args(h, E, bias, lo, hi, exclude):
+    B, d = h.shape
+    hi = E.shape[0] if hi is None else int(hi)
+    lo = int(lo)
+    if not 0 <= lo < hi <= E.shape[0]:
+        raise ValueError(f"item range [{lo}, {hi}) outside the table's [0, {E.shape[0]})")
+    if E.dtype != h.dtype or h.stride(1) != 1 or E.stride(1) != 1:
+        raise TypeError("h and E: rows of one dtype with unit element stride")
+    nx = 0
+    if exclude is not None and exclude.numel():
+        # the sweep binary-searches each row's list per vocabulary tile: sorted rows (rs_full_rank's contract)
+        exclude = torch.sort(exclude.reshape(B, -1).to(torch.int64), dim=1).values.contiguous()
+        nx = exclude.shape[1]
+    else:
+        exclude = None
+    return B, d, lo, hi, exclude, nx
+
+
+def full_ws(h, lo, hi, k):
+    """uint8 workspace of rs_full_ws_bytes for h's (B, d) against the item range [lo, hi) (k = 0: full_rank)."""
+    B, d = h.shape
+    n = int(_lib.lib().rs_full_ws_bytes(dtype_code(h), B, d, hi - lo, k))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=h.device)
+
+
+def full_rank(h, E, target, bias=None, lo=1, hi=None, exclude=None, return_scores=False, check=True):
+    """int32 (B,) rank of target[b] among the admissible items of [lo, hi) (hi: E's rows): the number of items v, not
+    in exclude[b] (int64 (B, n); zeros and ids outside the range are ignored; the target itself always stays), with
+    <h[b], E[v]> (+ bias[v]) above the target's score, or equal to it and v < target[b]: rs_full_rank.  h: (B, d)
+    rows (row stride may exceed d), E: (V, d) in h's dtype.  Raises IndexError for a target outside [lo, hi); with
+    check=False (no host read: inside a graph capture) such a row ranks -1 instead."""
+    B, d, lo, hi, exclude, nx = _full_args(h, E, bias, lo, hi, exclude)
+    target = target.to(torch.int64).contiguous()
+    if check and bool(((target < lo) | (target >= hi)).any()):
+        raise IndexError("target id outside the item range")
+    ws = full_ws(h, lo, hi, 0)
+    rank = torch.empty(B, dtype=torch.int32, device=h.device)
+    ts = torch.empty(B, dtype=torch.float32, device=h.device) if return_scores else None
+    call("rs_full_rank", dtype_code(h), ptr(h), h.stride(0), B, d, ptr(E), E.stride(0), ptr(bias), lo, hi,
+         ptr(target), ptr(exclude), nx, nx, ptr(ws), ptr(rank), ptr(ts), stream())
+    return (rank, ts) if return_scores else rank
+
+
+def full_topk(h, E, k, bias=None, lo=1, hi=None, exclude=None):
+    """(ids int64 (B, k), scores fp32 (B, k)): per row the k best admissible items of [lo, hi), by score descending
+    and id ascending among equal scores: rs_full_topk.  Past the number of admissible items: id -1, score -inf."""
+    k = int(k)
+    if not 1 <= k <= RS_TOPK_MAX:
+        raise ValueError(f"k must be in 1..{RS_TOPK_MAX}, got {k}")
+    B, d, lo, hi, exclude, nx = _full_args(h, E, bias, lo, hi, exclude)
+    ws = full_ws(h, lo, hi, k)
+    ids = torch.empty((B, k), dtype=torch.int64, device=h.device)
+    scores = torch.empty((B, k), dtype=torch.float32, device=h.device)
+    call("rs_full_topk", dtype_code(h), ptr(h), h.stride(0), B, d, ptr(E), E.stride(0), ptr(bias), lo, hi,
+         ptr(exclude), nx, nx, k, ptr(ws), ptr(ids), ptr(scores), stream())
+    return ids, scores
+
+
+def rank_to_metrics(rank, ks_dev, ws, out):
+    """out[3q + {0, 1, 2}] = mean Recall / NDCG / MRR @ ks_dev[q] of int32 ranks (one positive per row; -1: a miss);
+    ws: >= 3 * nk * rows floats (rs_rank_to_metrics)."""
+    call("rs_rank_to_metrics", ptr(rank), rank.numel(), ks_dev.numel(), ptr(ks_dev), ptr(ws), ptr(out), stream())
