@@ -40,7 +40,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
     const float keep = (mode == 0 && id == 0) ? 0.f : 1.f;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float x = mode == 0 ? e[j] * scale + p[j] : e[j] + p[j];
+      // one rounding (fma), spelled out: rs_sas_block_in_embed (rowchain.hip embed_tile) forms the same value, and
+      // left to the compiler the select between the two modes kept this one a separate multiply and add
+      float x = mode == 0 ? __builtin_fmaf(e[j], scale, p[j]) : e[j] + p[j];
       if (drop_p > 0.f) x *= drop_mul(drop_p, seed, (uint64_t)(r * d + c + j));
       o[j] = x * keep;
     }
@@ -65,7 +67,8 @@ __global__ __launch_bounds__(256) void embed_fwd_any_kernel(const int64_t* __res
   const int64_t r = i / d, c = i % d, t = r % T_;
   const int64_t id = ids[r];
   const float e = to_f(table[id * d + c]), p = to_f(pos[t * d + c]);
-  float x = mode == 0 ? e * scale + p : e + p;
+  // fma spelled out, as in embed_fwd_kernel (left to the compiler this one too was a multiply and an add)
+  float x = mode == 0 ? __builtin_fmaf(e, scale, p) : e + p;
   if (drop_p > 0.f) x *= drop_mul(drop_p, seed, (uint64_t)i);
   out[i] = from_f<T>((mode == 0 && id == 0) ? 0.f : x);
 }

@@ -561,8 +561,8 @@ __device__ __forceinline__ void embed_tile(Raw<D>& xr, const EmbIn& e, const Til
   for (int s = 0; s < Lay<D>::S; ++s)
 #pragma unroll
     for (int k = 0; k < 8; k += 2) {
-      float x0 = (float)ev[s][k] * e.scale + (float)pv[s][k];
-      float x1 = (float)ev[s][k + 1] * e.scale + (float)pv[s][k + 1];
+      float x0 = __builtin_fmaf(e.scale, (float)ev[s][k], (float)pv[s][k]);   // fma, as embed_fwd_kernel spells it
+      float x1 = __builtin_fmaf(e.scale, (float)ev[s][k + 1], (float)pv[s][k + 1]);
       if (e.drop_p > 0.f) {
         float m0, m1;
         drop_mul2(e.drop_p, s32, (uint64_t)(T.mc * D + 32 * s + 8 * g + k), m0, m1);

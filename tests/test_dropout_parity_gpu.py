@@ -135,6 +135,8 @@ def _check(grads, g64, flat, tol, d=None, kbias=None):
     ("bf16", 3416, 200, 50, 2, 1, 4),    # cfg1 in bf16 (generic kernels, unaligned rows)
     ("fp32", 400, 300, 64, 2, 1, 2),     # --max_len 300 (T > 256)
     ("bf16", 54542, 50, 128, 2, 1, 128), # cfg4 exactly (Amazon-Beauty shape): the benchmarked per-GPU step
+    ("bf16", 300, 50, 64, 1, 1, 700),    # M = 35,000 > 8 * 16 * 256 rows: the row-chain kernels' waves carry a second
+                                         # tile (fused step, embedding-in-block-in and head-in-block-out forms)
 ])
 def test_sas_dropout_step_matches_oracle(dtype, V, T, d, L, h, B):
     import rbm_amd.data as synth
