@@ -666,6 +666,32 @@ int rs_full_topk(int dtype, const void* h, int64_t ldh, int64_t B, int64_t d, co
                  void* ws, int64_t* ids, float* scores, void* stream);
 int rs_rank_to_metrics(const int* rank, int64_t rows, int nk, const int* ks, float* ws, float* out, void* stream);
 
+/* ---- SASRec tied full-catalogue cross-entropy head: the row kernels (sas_ce.hip; bf16, d in {64, 128}) ----
+ * The objective: f = LN_last(x_L), logits = f item_emb^T over all V+1 rows (class 0 = the zero padding row),
+ * CrossEntropyLoss(ignore_index=0) against pos.  The vocabulary part runs through rs_vocab_head_fwd / _bwd
+ * (bias NULL, E = item_emb) on the compacted valid rows; these are the row-local launches around it.  Both return
+ * RS_ERR_UNSUPPORTED, launching nothing, for any other dtype or width.
+ * rs_sas_ce_rows_fwd: rs_compact_rows(labels, M, cap) + rs_layernorm_fwd (variant 0) + rs_gather_rows in one launch:
+ *   idx [cap], rank [M], *count exactly as rs_compact_rows writes them; for i < *count, with r = idx[i]:
+ *   hl[i] = LN(x[r]) (bf16, row stride ldh), lab[i] = labels[r], mean[i], rstd[i] (fp32, per COMPACT row).  Rows
+ *   >= *count of hl / lab / mean / rstd are left untouched.  x: bf16 [M][d], row stride ldx (multiple of 8).
+ *   divisor (nullable): *divisor = max(*count, 1) as a float -- the count_override / count of the vocabulary
+ *   kernels, so that a batch with no valid row has loss 0 (0 / 1) instead of 0 / 0.
+ * rs_sas_ce_rows_nparts (host only): affine-partial sets rs_sas_ce_rows_bwd writes for M rows.
+ * rs_sas_ce_rows_bwd: rs_splitk_scatter_rows + rs_layernorm_bwd in one launch: for r < M with k = rank[r] >= 0,
+ *   dh = bf16(sum over z < splits, in order, of slab[z][k][:]) (slab fp32 [splits][cap][d]) and
+ *   dx[r] = LN'(x[r], dh; mean[k], rstd[k]); dx[r] = 0 where rank[r] < 0.  part[b][2][d] (b < nparts): the sums of
+ *   dh * xhat (dgamma) and dh (dbeta) over the rows of set b -- row r belongs to set (r / (2048 / d)) mod nparts --
+ *   to be reduced in set order (rs_reduce_segments; ops.ln_partial_segments).  No atomics. */
+int rs_sas_ce_rows_fwd(int dtype, int64_t M, int64_t d, const void* x, int64_t ldx, const int64_t* labels,
+                       int64_t cap, const float* gamma, const float* beta, float eps, int32_t* idx, int32_t* rank,
+                       int32_t* count, float* divisor, void* hl, int64_t ldh, int64_t* lab, float* mean, float* rstd,
+                       void* stream);
+int64_t rs_sas_ce_rows_nparts(int64_t M);
+int rs_sas_ce_rows_bwd(int dtype, int64_t M, int64_t d, const float* slab, int splits, int64_t cap,
+                       const int32_t* rank, const void* x, int64_t ldx, const float* gamma, const float* mean,
+                       const float* rstd, void* dx, int64_t lddx, float* part, void* stream);
+
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);
 

@@ -15,6 +15,9 @@ class SASModel(BaseModel):
     def forward(self, log_seqs, pos_seqs, neg_seqs):  # for training
         return self.sas(log_seqs, pos_seqs, neg_seqs)
 
+    def ce_loss(self, log_seqs, pos_seqs):  # full-catalogue softmax cross-entropy, item table tied (SAS.ce_loss)
+        return self.sas.ce_loss(log_seqs, pos_seqs)
+
     def predict(self, log_seqs, item_indices):  # for inference
         return self.sas.predict(log_seqs, item_indices)
 

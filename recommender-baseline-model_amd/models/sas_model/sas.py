@@ -20,11 +20,15 @@ rs_sas_block_in_bwd per block, then ONE grouped launch of every weight / bias / 
 (rs_wgrad_grouped_pos_stats, with the positional table's gradient and the loss statistics) beside the item-table
 gradient by inverted index (rs_item_index_build on a side stream during the forward, rs_item_grad), then the fused
 Adam (rs_adam_prepare_step_loss).
+loss="ce" (ce_forward / ce_backward): the blocks without the in-block head, then on the rows with pos != 0 only
+rs_sas_ce_rows_fwd -> rs_vocab_head_fwd / _bwd against the whole item table (tied) -> rs_linear_wgrad (dE) -> rs_gemm
+(dh) -> rs_sas_ce_rows_bwd, and the blocks' backward with the item index over the input ids alone.
 fp32 parity mode and other widths run the generic unfused kernels: rs_embed_fwd, rs_layernorm_fwd/bwd (variant 0,
 eps 1e-8), rs_gemm (MFMA, fused bias / ReLU / dropout / residual / row-mask epilogues), rs_attn_fwd/bwd,
 rs_sampled_logits_fwd/bwd, rs_bce_*, split-K weight gradients.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -34,6 +38,7 @@ from ...engine_util import Workspace, as_ids, capture_event, compute_dtype, requ
 from ...flat import FlatParams
 
 LN_EPS = 1e-8
+SAS_LOSSES = ("bce", "ce")
 
 
 class PointWiseFeedForward(nn.Module):
@@ -58,6 +63,11 @@ class SAS(nn.Module):
         self.dropout_rate = args.sas_dropout
         # the trainer's l2 regulariser weight (BS/trainers/sas.py:14,51-52), applied by FusedTrainStep
         self.l2_emb = float(getattr(args, "l2_emb", 0.0) or 0.0)
+        # the training objective FusedTrainStep takes by default: "bce" (the reference's one sampled negative per
+        # position) or "ce" (softmax cross-entropy over the whole catalogue, the item table tied as output layer)
+        self.sas_loss = str(getattr(args, "sas_loss", None) or "bce")
+        if self.sas_loss not in SAS_LOSSES:
+            raise ValueError(f"sas_loss must be one of {SAS_LOSSES}, got {self.sas_loss!r}")
         self.cdtype = compute_dtype(args)
         d = self.hidden
         if d % self.heads:
@@ -107,6 +117,21 @@ class SAS(nn.Module):
         params = [p for _, p in self.named_parameters()]
         return _SASFunction.apply(eng, ids, pos, neg, self.training, *params)
 
+    def ce_loss(self, log_seqs, pos_seqs):
+        """Scalar loss of the tied full-catalogue objective (differentiable; available whatever sas_loss says):
+
+            f = last_layernorm(log2feats(seq));  logits = f @ item_emb.weight.T      # (B, T, V+1), class 0 = padding
+            loss = F.cross_entropy(logits.view(-1, V+1), pos.view(-1), ignore_index=0)
+
+        the mean over the positions with pos != 0.  The padding row of the item table gets no gradient.  A batch
+        with no valid position gives loss 0 and all-zero gradients (torch gives NaN there).  The head's buffers are
+        the engine's workspace: call backward() before the next ce_loss()."""
+        eng = self.engine()
+        dev = self._flat.device
+        ids, pos = as_ids(log_seqs, dev), as_ids(pos_seqs, dev)
+        params = [p for _, p in self.named_parameters()]
+        return _SASCEFunction.apply(eng, ids, pos, self.training, *params)
+
     def log2feats(self, log_seqs):
         eng = self.engine()
         ids = as_ids(log_seqs, self._flat.device)
@@ -151,6 +176,25 @@ class _SASFunction(torch.autograd.Function):
         ctx.saved = None
         grads = [eng.flat.view(n, grad) for n in eng.flat.names]
         return (None, None, None, None, None, *grads)
+
+
+class _SASCEFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, ids, pos, training, *params):
+        engine.sync_compute_weights()
+        out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
+        ctx.saved = engine.ce_forward(ids, pos, training, out)
+        ctx.engine = engine
+        return out[2].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        eng = ctx.engine
+        grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
+        eng.ce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
+        ctx.saved = None
+        grads = [eng.flat.view(n, grad) for n in eng.flat.names]
+        return (None, None, None, None, *grads)
 
 
 class SASEngine:
@@ -215,12 +259,13 @@ class SASEngine:
 
     # ---- forward -------------------------------------------------------------------
     def forward(self, ids, pos, neg, training, need_logits=True, clone_seed=True, fuse_head=False,
-                head_divisor=None):
+                head_divisor=None, ce=False):
         """fuse_head (the fused training step, whose backward forms the BCE gradient itself): the head's forward
         and backward run as one pass per token inside the last block's output kernel (rs_sas_block_out_head); the
         returned pl / nl are filled by then.  The first block's input kernel counts the valid positions (the BCE
         divisor) for it; head_divisor (device scalar, data parallel: 1) replaces that count and must be the divisor
-        later passed to backward."""
+        later passed to backward.  ce (ce_forward): the blocks only -- no last LayerNorm, no sampled head; the
+        side branch indexes the input ids alone (neg plays no part)."""
         B, T = ids.shape
         M, d, H, Dh, L = B * T, self.d, self.H, self.Dh, self.L
         p = self.p if training else 0.0
@@ -235,6 +280,7 @@ class SASEngine:
              "x1": [], "z": [], "mu2": [], "r2": [], "h1": []}
         fused = ops.sas_block_fused_ok(d, self.dt)
         side = fused and training and pos is not None
+        nsrc = 1 if ce else 3
         if side:
             fork = capture_event()
             fork.record()
@@ -258,7 +304,7 @@ class SASEngine:
             if side:
                 # issued after the first forward launch: in the captured graph the forward chain is then the
                 # first child of the step's root and keeps the launch queue; the side branch gets the second
-                s["side"] = self._side_prologue(ids, pos, neg, after=fork)
+                s["side"] = self._side_prologue(ids, pos, neg, after=fork, nsrc=nsrc)
         head = None
         if cntp is not None:
             # the head inside the last block's output kernel: its outputs, per-workgroup partials
@@ -305,6 +351,9 @@ class SASEngine:
         if "head_in_block" in s:
             s.update(xL=x)
             return s["pl"], s["nl"], s
+        if ce:
+            s.update(xL=x)
+            return None, None, s
         f, muf, rf = e("f", (M, d)), e("mu", (M,), torch.float32), e("r", (M,), torch.float32)
         s.update(xL=x, f=f, muf=muf, rf=rf)
         if fused and need_logits:
@@ -455,6 +504,20 @@ class SASEngine:
         dx = e("dx", (M, d))
         ops.layernorm_bwd(s["xL"], df, self.Wf("last_layernorm.weight"), s["muf"], s["rf"], LN_EPS, dx,
                           G("last_layernorm.weight"), G("last_layernorm.bias"), wln, 0)
+        self._backward_blocks_unfused(s, dx, grad, by_index, [ids, s["pos"], s["neg"]], s["f"], dpl, dnl)
+
+    def _backward_blocks_unfused(self, s, dx, grad, by_index, keys, f, w1, w2):
+        """The generic (fp32 parity / other widths) blocks' backward from dx = the gradient at the last block's
+        output, then the embedding tables' gradients.  by_index: the item table's by the inverted index over `keys`
+        (the input ids, then the tied head's pos / neg with weights w1 / w2 on f); else the atomic scatter."""
+        B, T, p, ids = s["B"], s["T"], s["p"], s["ids"]
+        M, d, H, Dh, L = B * T, self.d, self.H, self.Dh, self.L
+        sb = s["sb"]
+        e = self._buf
+        G = lambda n: self.flat.view(n, grad)  # noqa: E731
+        slab = self.ws.get("slab", (ops.wgrad_slab_numel(M, 2 * d, d),), torch.float32)
+        wln = self.ws.get("ln", (2 * 512 * d,), torch.float32)
+        wat = self.ws.get("attn", (B * H * T,), torch.float32)
         for i in reversed(range(L)):
             pre = f"attention_layers.{i}."
             fw = f"forward_layers.{i}."
@@ -496,10 +559,141 @@ class SASEngine:
                       G("pos_emb.weight"))
         if by_index:
             V1 = self.flat.shapes["item_emb.weight"][0]
-            iws = self.ws.get("itemidx", (ops.item_index_ws_bytes(3, M, V1, d),), torch.uint8)
-            ops.item_index_build([ids, s["pos"], s["neg"]], V1, d, iws)
-            ops.item_grad(iws, 3, M, dx, math.sqrt(d), p, self.salt["emb"], sb, s["f"], dpl, dnl,
-                          G("item_emb.weight"), marks=getattr(self, "row_marks", None))
+            n = len(keys)
+            iws = self.ws.get("itemidx", (ops.item_index_ws_bytes(n, M, V1, d),), torch.uint8)
+            ops.item_index_build(keys, V1, d, iws)
+            ops.item_grad(iws, n, M, dx, math.sqrt(d), p, self.salt["emb"], sb, f, w1, w2,
+                          G("item_emb.weight"), marks=getattr(self, "row_marks", None) if n == 3 else None)
+
+    # ---- tied full-catalogue cross-entropy head ---------------------------------------
+    @property
+    def ce_rows_fused(self):
+        """True when the CE head's row-local work runs in the two sas_ce.hip launches (bf16, d in {64, 128});
+        RS_SAS_CE_ROWS=0 selects the composed launches they replace (A/B timing, tools/sas_ce_bench.py)."""
+        return ops.sas_ce_rows_ok(self.d, self.dt) and os.environ.get("RS_SAS_CE_ROWS", "1") != "0"
+
+    def ce_forward(self, ids, pos, training, loss_out, max_labelled=None, clone_seed=True):
+        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and CrossEntropy(ignore_index=0)
+        of the logits against the whole item table (tied; class 0 is the zero padding row), never materialised in
+        bf16.  loss_out (fp32 [>= 3], device) = {loss sum, valid count, mean}; a batch without a valid row gives
+        mean 0.  max_labelled: upper bound on the valid rows (sizes the compact buffers; default B*T; rows past it
+        are dropped as rs_compact_rows does).  Returns the saved state for ce_backward.  Buffers are the engine's
+        workspace; nothing here allocates per step or reads the host."""
+        d, dt = self.d, self.dt
+        if dt == torch.bfloat16 and d % 8:
+            raise ValueError(f"the bf16 cross-entropy head needs hidden units divisible by 8 (got {d}); "
+                             "use fp32 mode (rs_dtype='fp32') at this width")
+        B, T = ids.shape
+        M = B * T
+        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
+        f32 = torch.float32
+        g = self.ws.get
+        # fp32 rows that are no multiple of 16 bytes (the reference's d = 50): the compaction kernels do not take
+        # them, so the head runs on all M rows (labels 0 are ignored by rs_ce_fwd / rs_ce_bwd: same loss, same
+        # gradients)
+        dense = dt == torch.float32 and d % 4 != 0
+        cap = M if dense else int(max_labelled or M)
+        V1 = self.flat.shapes["item_emb.weight"][0]
+        V1p = -(-V1 // 64) * 64
+        x, labels = s["xL"], pos.reshape(-1)
+        idx, rank, cnt = g("ce_idx", (cap,), torch.int32), g("ce_rank", (M,), torch.int32), g("ce_cnt", (1,), torch.int32)
+        if "ce_hl" not in self.ws.bufs or tuple(self.ws.bufs["ce_hl"].shape) != (cap, d):
+            g("ce_hl", (cap, d), dt).zero_()      # rows past the live count are never written: start them finite
+        hl, lab, div = g("ce_hl", (cap, d), dt), g("ce_lab", (cap,), torch.int64), g("ce_div", (1,), f32)
+        E = self.W("item_emb.weight")
+        gl, bl = self.Wf("last_layernorm.weight"), self.Wf("last_layernorm.bias")
+        rows_fused = self.ce_rows_fused
+        if dense:
+            hl, mu, rs, lab, cnt = g("ce_f", (M, d), dt), g("ce_mu", (M,), f32), g("ce_rs", (M,), f32), labels, None
+            ops.layernorm_fwd(x, gl, bl, LN_EPS, hl, mu, rs, 0)
+            div.copy_(torch.count_nonzero(labels)).clamp_(min=1)
+        elif rows_fused:
+            mu, rs = g("ce_mu", (cap,), f32), g("ce_rs", (cap,), f32)
+            ops.sas_ce_rows_fwd(x, labels, cap, gl, bl, LN_EPS, idx, rank, cnt, hl, lab, mu, rs, divisor=div)
+        else:
+            f, mu, rs = g("ce_f", (M, d), dt), g("ce_mu", (M,), f32), g("ce_rs", (M,), f32)
+            ops.layernorm_fwd(x, gl, bl, LN_EPS, f, mu, rs, 0)
+            ops.compact_rows(labels, cap, idx, rank, cnt)
+            ops.gather_rows(f, idx, cnt, cap, hl, labels, lab)
+            div.copy_(cnt).clamp_(min=1)          # the mean's divisor: max(count, 1)
+        if dt == torch.bfloat16:
+            wce = g("ce_vce", (ops.vocab_ce_ws_numel(cap, V1),), f32)
+            fwd = ops.vocab_head_fwd if ops.vocab_head_supported(d) else ops.vocab_ce_fwd
+            fwd(hl, E, None, lab, wce, loss_out, rows_dev=cnt, count_override=div)
+            dl = None
+        else:
+            dl = g("ce_logits", (cap, V1p), f32)[:, :V1]          # the logits, then dlogits in place
+            ops.linear_fwd(hl, E, dl, rows_dev=cnt)
+            wce = g("ce_wce", (3 * cap,), f32)
+            ops.ce_fwd(dl, lab, wce, loss_out, div, rows_dev=cnt)
+        s.update(ce=dict(cap=cap, V1=V1, V1p=V1p, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, mu=mu, rs=rs, wce=wce,
+                         dl=dl, rows_fused=rows_fused, dense=dense))
+        return s
+
+    def ce_backward(self, s, grad, dloss=None):
+        """Accumulates every parameter gradient of ce_forward's loss (times *dloss, a device scalar, if given) into
+        the flat fp32 buffer ``grad``.  The item table's gradient has two parts: the dense dlogits^T f over all
+        rows (rs_linear_wgrad's fixed-order split-K, row 0 cleared afterwards: the padding row gets no gradient),
+        written on the main stream BEFORE the blocks' backward, and the lookup part by the inverted index over the
+        input ids (rs_item_grad, one writer per row), which the fused path runs on the side stream only after the
+        blocks' backward: one writer at a time, fixed order, no float atomics."""
+        c = s["ce"]
+        B, T, p, ids = s["B"], s["T"], s["p"], s["ids"]
+        M, d = B * T, self.d
+        sb, dt = s["sb"], self.dt
+        f32 = torch.float32
+        g = self.ws.get
+        G = lambda n: self.flat.view(n, grad)  # noqa: E731
+        cap, V1, cnt, hl, lab = c["cap"], c["V1"], c["cnt"], c["hl"], c["lab"]
+        E = self.W("item_emb.weight")
+        if dt == torch.bfloat16:
+            dl = g("ce_dlogits", (cap, c["V1p"]), dt)[:, :V1]     # the one (cap, V+1) buffer of the bf16 path
+            bwd = ops.vocab_head_bwd if ops.vocab_head_supported(d) else ops.vocab_ce_bwd
+            bwd(hl, E, None, lab, c["wce"], c["div"], dl, rows_dev=cnt, dloss=dloss)
+        else:
+            dl = c["dl"]
+            ops.ce_bwd(dl, lab, c["div"], dloss, c["wce"], dl, rows_dev=cnt)
+        GE = G("item_emb.weight")
+        slab = g("ce_slab_dE", (ops.wgrad_slab_numel(cap, V1, d),), f32)
+        ops.linear_wgrad(dl, hl, GE, slab, rows_dev=cnt, accumulate=True)
+        GE[0].zero_()                              # class 0 is the padding row: no gradient (padding_idx)
+        # dh = dlogits E: a contraction over the whole catalogue with few rows -- split-K into fp32 slabs
+        sk = int(max(1, min(64, -(-V1 // 2048))))
+        slab_d = g("ce_slab_dh", (sk * cap * d,), f32)
+        ops.gemm(dl, E, slab_d, cap, d, V1, False, True, ops.epilogue(rows_dev=cnt), split_k=sk, slab=slab_d)
+        gl = self.Wf("last_layernorm.weight")
+        fused = ops.sas_block_fused_ok(d, dt)
+        dx = g("ce_dx", (M, d), dt)
+        if c["rows_fused"]:
+            nb = ops.sas_ce_rows_nparts(M)
+            part = g("ce_lnp", (2 * d * nb,), f32)
+            ops.sas_ce_rows_bwd(slab_d, sk, cap, c["rank"], s["xL"], gl, c["mu"], c["rs"], dx, part)
+            segs = ops.ln_partial_segments(part, M, d, G("last_layernorm.weight"), G("last_layernorm.bias"), nb=nb)
+            if not fused:
+                ops.reduce_segments(segs)
+        else:
+            df = g("ce_df", (M, d), dt)
+            if c["dense"]:
+                ops.reduce_slabs(slab_d, sk, df)
+            else:
+                ops.splitk_scatter_rows(slab_d, sk, cap, c["rank"], df)
+            wln = g("ln", (2 * 512 * d,), f32)
+            ops.layernorm_bwd(s["xL"], df, gl, c["mu"], c["rs"], LN_EPS, dx, G("last_layernorm.weight"),
+                              G("last_layernorm.bias"), wln, 0)
+            segs = []
+        if not fused:
+            by_index = dt == torch.float32 or d in (64, 128, 256)
+            self._backward_blocks_unfused(s, dx, grad, by_index, [ids], None, None, None)
+            return
+        ev, iws = s["side"] if "side" in s else self._side_prologue(ids, None, None, nsrc=1)
+        if self._side_refreshed:
+            torch.cuda.current_stream().wait_event(ev)
+
+        def item_grads(dx):
+            ops.item_grad(iws, 1, M, dx, math.sqrt(d), p, self.salt["emb"], sb, None, None, None, GE)
+        self._backward_blocks_fused(s, dx, grad, segs, tail=item_grads,
+                                    pos=lambda dx: (ids, T, dx, p, self.salt["emb"], sb, G("pos_emb.weight")))
+        torch.cuda.current_stream().wait_event(self._tail_join)
 
     def enable_row_marks(self, min_rows=0):
         """Stamp the rows the inverted-index gradient writes (rs_item_grad_marked) so the optimizer can skip the
@@ -514,7 +708,7 @@ class SASEngine:
                           torch.zeros(1, dtype=torch.uint8, device=self.dev))
         return (name,) + self.row_marks
 
-    def _side_prologue(self, ids, pos, neg, after=None):
+    def _side_prologue(self, ids, pos, neg, after=None, nsrc=3):
         """Work of the fused backward that depends only on the batch's keys and the weights, issued on a
         side stream so it overlaps the forward pass: the item-gradient index (rs_item_index_build) and
         the transposed block weights (rs_transpose_bf16).  Returns (event, index workspace)."""
@@ -529,8 +723,8 @@ class SASEngine:
         M, d = B * T, self.d
         V1 = self.flat.shapes["item_emb.weight"][0]
         with torch.cuda.stream(self._side):
-            iws = self.ws.get("itemidx", (ops.item_index_ws_bytes(3, M, V1, d),), torch.uint8)
-            ops.item_index_build([ids, pos, neg], V1, d, iws)
+            iws = self.ws.get("itemidx", (ops.item_index_ws_bytes(nsrc, M, V1, d),), torch.uint8)
+            ops.item_index_build([ids, pos, neg][:nsrc], V1, d, iws)
             self._side_refreshed = not self.adam_transposes or self._wT is None
             if self._side_refreshed:
                 self._refresh_transposed()

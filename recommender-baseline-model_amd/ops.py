@@ -765,6 +765,37 @@ def sas_head_bwd(part, divisor, out, pl, nl, dpl_in, dnl_in, dpl, dnl, pos, neg,
          ptr(lnpart), stream())
 
 
+# ---- SAS tied full-catalogue CE head: the row kernels (sas_ce.hip) --------------------------
+def sas_ce_rows_ok(d, dtype):
+    """The widths rs_sas_ce_rows_fwd / _bwd cover (the fused engine's: bf16, d in {64, 128})."""
+    return dtype == torch.bfloat16 and d in (64, 128)
+
+
+def sas_ce_rows_fwd(x, labels, cap, ln_w, ln_b, eps, idx, rank, count, hl, lab, mean, rstd, divisor=None):
+    """compact_rows(labels) + the last LayerNorm on the valid rows of x only + gather, one launch: hl [cap][d],
+    lab [cap], mean / rstd [cap] per compact row; rows >= count are left untouched.  divisor (fp32 [1]): receives
+    max(count, 1), the CE mean's divisor."""
+    M, d = x.shape
+    assert labels.numel() == M and hl.shape[0] >= cap and rank.numel() >= M and idx.numel() >= cap
+    call("rs_sas_ce_rows_fwd", dtype_code(x), M, d, ptr(x), ld(x), ptr(labels), cap, ptr(ln_w), ptr(ln_b), eps,
+         ptr(idx), ptr(rank), ptr(count), ptr(divisor), ptr(hl), ld(hl), ptr(lab), ptr(mean), ptr(rstd), stream())
+
+
+def sas_ce_rows_nparts(M):
+    """LayerNorm affine partial sets sas_ce_rows_bwd leaves for M rows (host only)."""
+    return int(_lib.lib().rs_sas_ce_rows_nparts(M))
+
+
+def sas_ce_rows_bwd(slab, splits, cap, rank, x, ln_w, mean, rstd, dx, part):
+    """Split-K sum of dh (slab fp32 [splits][cap][d], fixed order) + LayerNorm backward + scatter to all rows of dx
+    (zeros at invalid rows); part [nparts][2][d]: the affine partials (ln_partial_segments(nb=nparts))."""
+    M, d = x.shape
+    assert slab.numel() >= splits * cap * d and part.numel() >= 2 * d * sas_ce_rows_nparts(M)
+    assert dx.shape == (M, d) and rank.numel() >= M
+    call("rs_sas_ce_rows_bwd", dtype_code(x), M, d, ptr(slab), splits, cap, ptr(rank), ptr(x), ld(x), ptr(ln_w),
+         ptr(mean), ptr(rstd), ptr(dx), ld(dx), ptr(part), stream())
+
+
 def sas_head_finish(part, divisor, out):
     """Loss statistics out[0..3] from the head's BCE partials part[nblk][3] (one workgroup)."""
     call("rs_sas_head_finish", part.numel() // 3, ptr(part), ptr(divisor), ptr(out), stream())

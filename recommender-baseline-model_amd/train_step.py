@@ -158,12 +158,15 @@ class FusedStepLR:
 
 class FusedTrainStep:
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
-                 bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto"):
+                 bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None):
         """model: rbm_amd SASModel or BERTModel on a CUDA device.
         dp: data-parallel mode (default: torch.distributed initialised with world size > 1).
-        max_labelled (BERT): upper bound on labelled rows per batch (sizes the compacted
-        vocabulary-logit buffers; default B*T).  overlap (DP, default on unless bucket_numel is given): each
-        gradient bucket's all-reduce starts as soon as the backward has finished it (dp.BucketedExchange);
+        max_labelled (BERT; SAS with loss="ce": the valid rows, pos != 0): upper bound on labelled rows per batch
+        (sizes the compacted vocabulary-logit buffers; default B*T).
+        loss (SAS): "bce" (the reference's sampled objective) or "ce" (softmax cross-entropy over the whole
+        catalogue with the item table as output layer, SASModel.ce_loss); None = the model's args.sas_loss.  With
+        "ce" the batch's neg plays no part and may be None; single device only.
+        overlap (DP, default on unless bucket_numel is given): each gradient bucket's all-reduce starts as soon as the backward has finished it (dp.BucketedExchange);
         bucket_numel: otherwise ONE all-reduce after the backward, in buckets of that many floats.
         vocab_shard (BERT, DP): out.weight / out.bias sharded over the ranks (rbm_amd.vocab_parallel).
         sparse_rows (BERT, DP with overlap): "auto" (default: when the gathered ids are at most half the table),
@@ -176,6 +179,16 @@ class FusedTrainStep:
         them (needs l2_emb == 0: the regulariser reads every master row)."""
         self.model = model
         self.kind = model.code()
+        if loss is None:
+            loss = getattr(model.sas, "sas_loss", "bce") if self.kind == "sas" else None
+        if self.kind == "sas":
+            if loss not in ("bce", "ce"):
+                raise ValueError(f"loss must be 'bce' or 'ce', got {loss!r}")
+        elif loss is not None:
+            raise ValueError(f"loss={loss!r} needs a SAS model (the BERT step has one objective)")
+        self.loss = loss
+        if loss == "ce" and (dpx.world() > 1 if dp is None else bool(dp)):
+            raise ValueError("FusedTrainStep(loss='ce') runs on a single device (data parallel is not covered)")
         self.engine = model.sas.engine() if self.kind == "sas" else model.engine()
         self.flat = self.engine.flat
         self.engine.sync_compute_weights()
@@ -276,7 +289,10 @@ class FusedTrainStep:
         # which stamp the rows they write; the optimizer then reads the gradient of those rows only (4 of its 30
         # bytes per element elsewhere).  Not under data parallel (other ranks' rows arrive by the exchange) nor
         # with the l2 regulariser (it writes every row); tables below ROW_MARKS_MIN rows are mostly touched.
-        if (not self.dp and not self.l2 and os.environ.get("RS_ROW_MARKS", "1") != "0"
+        # Nor with the full-catalogue CE loss: every table row then has a non-zero gradient.
+        if self.loss == "ce":
+            self.engine.row_marks = None
+        if (not self.dp and not self.l2 and self.loss != "ce" and os.environ.get("RS_ROW_MARKS", "1") != "0"
                 and hasattr(self.engine, "enable_row_marks")):
             r = self.engine.enable_row_marks(self.ROW_MARKS_MIN)
             if r is not None:
@@ -371,7 +387,11 @@ class FusedTrainStep:
                 if action is None:
                     write_aux()
                 split(tag, action)
-        if self.kind == "sas":
+        if self.kind == "sas" and self.loss == "ce":
+            seq, pos = batch[0], batch[1]
+            saved = eng.ce_forward(seq, pos, True, self.loss_out, max_labelled=self.max_labelled, clone_seed=False)
+            eng.ce_backward(saved, self.flat.grad)
+        elif self.kind == "sas":
             seq, pos, neg = batch
             pl, nl, saved = eng.forward(seq, pos, neg, True, clone_seed=False, fuse_head=eng.fused_head,
                                         head_divisor=self.one if self.dp else None)
@@ -522,10 +542,17 @@ class FusedTrainStep:
             self._early_ev = capture_event()
             self._early_ev.record(self._opt_stream)
 
+    def _batch(self, batch):
+        """loss="ce": neg is ignored and may be None -- pos stands in, so the (seq, pos, neg) buffers keep their form."""
+        if self.loss == "ce" and (len(batch) == 2 or batch[2] is None):
+            return (batch[0], batch[1], batch[1])
+        return batch
+
     # ---------------------------------------------------------------- one step
     def step(self, *batch):
         """batch: SAS (seq, pos, neg) / BERT (tokens, labels) int64 device tensors.  Returns the
         device loss (the global batch's mean loss, as the reference's calculate_loss)."""
+        batch = self._batch(batch)
         if self.overlap:
             self._compute(*batch, split=self._eager_split, update=True)
             self.exchange.launch("final")
@@ -664,6 +691,7 @@ class FusedTrainStep:
         own Adam update -- are unrolled into ONE graph, so a replay costs one launch and one input copy per S
         steps; replay_packed() then takes the S batches stacked as [S, n_inputs, ...] and returns the S
         steps' losses."""
+        example_batch = self._batch(example_batch)
         S = self._unroll_check(steps_per_graph)
         # one packed static buffer when the inputs share shape and dtype: replay_packed() then refills
         # all of them with ONE device copy (the bench stacks its batches the same way)
@@ -974,6 +1002,7 @@ class FusedTrainStep:
     def replay(self, *batch):
         if self.steps_per_graph > 1:
             raise ValueError("an unrolled graph (steps_per_graph > 1) replays through replay_packed()")
+        batch = self._batch(batch)
         for dst, src in zip(self.static, batch):
             dst.copy_(src, non_blocking=True)
         return self._replay_graphs()
