@@ -487,6 +487,34 @@ int rs_sas_block_out_bwd_delta(int64_t M, int64_t d, const void* dxn, const int6
 int rs_sas_block_in_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
                         const float* mean1, const float* rstd1, const float* ln_w, const void* WinT, void* dx,
                         float* part, void* stream);
+/* Block-boundary launches (rowchain.hip): two adjacent row chains of the step in ONE launch, the tensor handed from
+ * the first to the second kept in registers.  The argument lists are the unions of the two entries they replace and
+ * the results are bitwise those of the two entries called back to back, for every M: the one-launch kernels run
+ * where every wave of the grid owns at most one 16-row tile (rs_sas_block_boundary_fused(M, d) == 1: d in {64, 128}
+ * and M <= 128 * CUs), the two single-block kernels are launched on the stream otherwise.
+ *   rs_sas_block_out_in: rs_sas_block_out of block i (every saved tensor still stored, xn included: it is block
+ *     i+1's saved input), then rs_sas_block_in(x = xn) with block i+1's ln1_w/ln1_b/eps1, Wq/bq, Wkv/bkv ->
+ *     Qn, mean1, rstd1, q, kv.
+ *   rs_sas_block_in_out_bwd: rs_sas_block_in_bwd of block i (LN1 partials -> part1), then
+ *     rs_sas_block_out_bwd_delta(dxn = dx) of block i-1 (h1, x1, mean2, rstd2, ln2_w, W*T, outputs dy2, da1, dx1o,
+ *     dout, LN2 partials -> part2, optional o/delta).  In the one-launch kernel dx is NOT written; the dx scratch
+ *     [M][d] is used only by the two-launch path and may be NULL when rs_sas_block_boundary_fused(M, d) (RS_ERR_ARG
+ *     if it is NULL and needed).
+ * RS_ERR_UNSUPPORTED for other d. */
+int rs_sas_block_boundary_fused(int64_t M, int64_t d);
+int rs_sas_block_out_in(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo, void* x1,
+                        const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
+                        const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
+                        const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2, const uint64_t* seed_base,
+                        const float* ln1_w, const float* ln1_b, float eps1, void* Qn, float* mean1, float* rstd1,
+                        const void* Wq, const float* bq, void* q, const void* Wkv, const float* bkv, void* kv,
+                        void* stream);
+int rs_sas_block_in_out_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
+                            const float* mean1, const float* rstd1, const float* ln1_w, const void* WinT, void* dx,
+                            float* part1, const int64_t* ids, const void* h1, const void* x1, const float* mean2,
+                            const float* rstd2, const float* ln2_w, const void* W2T, const void* W1T, const void* WoT,
+                            void* dy2, void* da1, void* dx1o, void* dout, float* part2, float drop_p, uint64_t salt1,
+                            uint64_t salt2, const uint64_t* seed_base, const void* o, float* delta, void* stream);
 /* Batched bf16 transpose: for m < nmat, desc[6m..6m+5] = {rows, cols, src_off, lds, dst_off, ldd}
  * (elements): dst[dst_off + c*ldd + r] = src[src_off + r*lds + c].  Grid x = max_tiles >= the
  * largest ceil(rows/64)*ceil(cols/64). */

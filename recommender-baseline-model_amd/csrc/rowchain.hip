@@ -232,6 +232,11 @@ __device__ __forceinline__ void ln_bwd(Act<D>& dy, const Raw<D>& xr, bool valid,
   sg = row_sum(sg);
   sgu = row_sum(sgu);
   const float mg = sg / (float)D, coef = a * a * a * sgu / (float)D;
+  // dy*g as a value of its own: whether the compiler folds its multiply into the subtraction below (an fma, one
+  // rounding less) depended on how the kernel around this stage laid out the cl == 0 updates above, and the stage
+  // must compute the same bits in every kernel that inlines it.  No instruction is emitted.
+#pragma unroll
+  for (int j = 0; j < Lay<D>::J; ++j) asm volatile("" : "+v"(dy.v[j]));
 #pragma unroll
   for (int j = 0; j < Lay<D>::J; ++j)
 #pragma unroll
@@ -399,11 +404,11 @@ __device__ __forceinline__ void fwd_out_a(const Raw<D>& orr, const Raw<D>& Qr, c
   if (!RC_NOSTORE) store_raw<D>(o.h1, D, T.m, T.ok, hr, g);
 }
 // part 2 (sas.py:81-84): x' = (drop(h1 W2^T + b2) + z) * (ids != 0) [saved] -> xr
+// (keep = T.ok && ids[T.mc] != 0: given by a caller that has requested the id earlier)
 template <int D>
 __device__ __forceinline__ void fwd_out_b(const Raw<D>& hr, const Raw<D>& zr, const Tile& T, const bf16* w2,
-                                          const float* lv, const OutFwd& o, Raw<D>& xr, int lane) {
+                                          const float* lv, const OutFwd& o, Raw<D>& xr, int lane, bool keep) {
   const int g = lane >> 4;
-  const bool keep = T.ok && o.ids[T.mc] != 0;
   Act<D> acc;
   zero<D>(acc);
   mm<D>(w2, hr, acc, lane);
@@ -421,6 +426,11 @@ __device__ __forceinline__ void fwd_out_b(const Raw<D>& hr, const Raw<D>& zr, co
   }
   round_act<D>(acc, xr);
   store_raw<D>(o.xn, D, T.m, T.ok, xr, g);
+}
+template <int D>
+__device__ __forceinline__ void fwd_out_b(const Raw<D>& hr, const Raw<D>& zr, const Tile& T, const bf16* w2,
+                                          const float* lv, const OutFwd& o, Raw<D>& xr, int lane) {
+  fwd_out_b<D>(hr, zr, T, w2, lv, o, xr, lane, T.ok && o.ids[T.mc] != 0);
 }
 
 // Backward, block input side (sas.py:73-76 reversed), part 1: dx_kv = dk Wk + dv Wv (WkT, WvT images)
@@ -461,11 +471,11 @@ struct OutBwd {
 };
 // Backward, block output side (sas.py:75-84 reversed), part 1: dzres = dxn*mask; dy2 = drop2(dzres) [saved];
 // da1 = relu'(h1) * drop1(dy2 W2) [saved] -> dz (holding dzres), dar (da1)
+// (keep = T.ok && ids[T.mc] != 0: given by a caller that has requested the id earlier)
 template <int D>
 __device__ __forceinline__ void bwd_out_a(const Raw<D>& dr, const Raw<D>& hr, const Tile& T, const bf16* w2,
-                                          const OutBwd& o, Raw<D>& dzr, Raw<D>& dar, int lane) {
+                                          const OutBwd& o, Raw<D>& dzr, Raw<D>& dar, int lane, bool keep) {
   const int g = lane >> 4;
-  const bool keep = T.ok && o.ids[T.mc] != 0;
   const bool drop = o.drop_p > 0.f;
   Act<D> acc;
   Raw<D> r;
@@ -493,6 +503,11 @@ __device__ __forceinline__ void bwd_out_a(const Raw<D>& dr, const Raw<D>& hr, co
   }
   round_act<D>(acc, dar);
   store_raw<D>(o.da1, D, T.m, T.ok, dar, g);
+}
+template <int D>
+__device__ __forceinline__ void bwd_out_a(const Raw<D>& dr, const Raw<D>& hr, const Tile& T, const bf16* w2,
+                                          const OutBwd& o, Raw<D>& dzr, Raw<D>& dar, int lane) {
+  bwd_out_a<D>(dr, hr, T, w2, o, dzr, dar, lane, T.ok && o.ids[T.mc] != 0);
 }
 // part 2: dz = da1 W1 + dzres; dx1 = LN2'(x1, dz) [saved, + affine partials into red]; dout = dx1 Wo [saved];
 // with o.delta: delta = rowsum(dout * O) of the stored (bf16) values, O = the attention output (orr)
@@ -936,6 +951,189 @@ __global__ __launch_bounds__(NT) void block_in_bwd_kernel(InBwdArgs a) {
   ln_partials<D>(red, a.part, tid);
 }
 
+// ------------------------------------------------------------------ block-boundary kernels
+// Two adjacent launches of the step are one per-row chain cut by a launch boundary: block i's output side and block
+// i+1's input side (forward), block i's input-side backward and block i-1's output-side backward (backward).  Both
+// kernels of a pair deal tiles with tiles_of_wave on the same grid, so the wave that forms a tile's hand-off tensor
+// (xn / dx) is the wave that consumes it: the kernels below run both chains on the rounded tile in registers, with
+// the stages above unchanged (same operations on the same rounded values in the same order: bitwise the composed
+// launches' results).  They exist only where every wave owns AT MOST ONE tile (n_tiles <= grid x NW; the entry
+// points launch the two single-block kernels otherwise), so a wave's chain is straight-line code and workgroup
+// barriers can sit between its stages.
+//
+// LDS: six weight images.  At D = 64 all six are staged at the start (48 KB).  At D = 128 (192 KB of images, 160 KB
+// of LDS) four slots roll: phase A's three images and the FIRST image of phase B are requested at the start; after
+// the barrier that every wave passes once it is done with slots 0 and 1, those two are re-staged with phase B's other
+// two images (the LDS-DMA runs under what is left of phase A and under phase B's first GEMM), and a second barrier
+// publishes them.  Waves without a tile take part in the staging and in every barrier.
+//
+// Every slot, the vectors and the partial blocks are SEPARATE static __shared__ arrays, not offsets into one dynamic
+// block: the compiler orders an LDS read after an outstanding LDS-DMA with s_waitcnt vmcnt(0) unless it can prove
+// the two touch different LDS objects, and with one block the re-stage would be waited for at the very next weight
+// fragment read instead of at the second barrier.
+template <int D> struct Roll {
+  static constexpr bool ON = 6 * Lay<D>::WBYTES > 128 * 1024;
+  static constexpr int WB = Lay<D>::WBYTES, XB = ON ? 16 : Lay<D>::WBYTES;   // slots 4, 5 exist only without rolling
+};
+template <int D>
+__device__ __forceinline__ void stage_slot(char* slot, const bf16* W, int64_t ldw, int wave, int lane) {
+  const bf16* const Wm[1] = {W};
+  const int64_t ld[1] = {ldw};
+  stage_w<D, 1>(slot, Wm, ld, wave, lane);
+}
+__device__ __forceinline__ const bf16* wimg(const char* slot) { return reinterpret_cast<const bf16*>(slot); }
+// The hand-off tile, made opaque to the optimizer.  The compiler fuses multiply-adds and pairs packed-math operands
+// by what it sees around them: with the producing stage's arithmetic visible the consuming stage's LayerNorm sum of
+// squares came out fused differently than in the single-block kernel (rstd 1 ulp apart).  Behind this the consumer
+// sees what the single-block kernel sees after its load -- eight opaque bf16 per register quad -- and is compiled the
+// same way (held bitwise by tests/test_rowchain_boundary_gpu.py).  No instruction is emitted.
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+template <int D>
+__device__ __forceinline__ void as_loaded(Raw<D>& r) {
+#pragma unroll
+  for (int s = 0; s < Lay<D>::S; ++s) {
+    u32x4 t = __builtin_bit_cast(u32x4, r.v[s]);
+    asm volatile("" : "+v"(t));
+    r.v[s] = __builtin_bit_cast(bf16x8, t);
+  }
+}
+#define RC_BOUNDARY_SLOTS(D)                                                                            \
+  __shared__ __attribute__((aligned(16))) char w0[Roll<D>::WB], w1[Roll<D>::WB], w2[Roll<D>::WB], w3[Roll<D>::WB], \
+      w4[Roll<D>::XB], w5[Roll<D>::XB]
+
+// o (block i) -> block_out_kernel<D, false>'s chain -> xn [saved] -> block_in_kernel's chain with block i+1's weights
+template <int D>
+__global__ __launch_bounds__(NT) void block_out_in_kernel(OutArgs a, InArgs b) {
+  typedef Roll<D> R;
+  RC_BOUNDARY_SLOTS(D);
+  __shared__ __attribute__((aligned(16))) float lv[10 * D];   // bo, ln2_w, ln2_b, b1, b2 | ln1_w, ln1_b, bq, bk, bv
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4,
+            cl = lane & 15;
+  const TileRange tr = tiles_of_wave(n_tiles(a.M), wave);
+  const bool has = tr.first < tr.end;   // this wave's one tile
+  const Tile T = tile_of(has ? tr.first : 0, a.M, cl);
+  const OutFwd of = out_fwd_of(a);
+  Raw<D> orr, Qr;
+  int64_t id = 0;   // requested here: a load issued after the re-stage would be waited for together with it
+  if (has) {
+    load_raw<D>(orr, a.o, D, T.mc, g);
+    load_raw<D>(Qr, a.Q, D, T.mc, g);
+    id = a.ids[T.mc];
+  }
+  const bf16* const Wk = b.Wkv;
+  const bf16* const Wv = b.Wkv + (int64_t)D * D;
+  stage_slot<D>(w0, a.Wo, D, wave, lane);
+  stage_slot<D>(w1, a.W1, D, wave, lane);
+  stage_slot<D>(w2, a.W2, D, wave, lane);
+  stage_slot<D>(w3, b.Wq, D, wave, lane);
+  if constexpr (!R::ON) {
+    stage_slot<D>(w4, Wk, D, wave, lane);
+    stage_slot<D>(w5, Wv, D, wave, lane);
+  }
+  {
+    const float* const V[10] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2, b.ln_w, b.ln_b, b.bq, b.bkv, b.bkv + D};
+    stage_v<D, 10>(lv, V, tid);
+  }
+  __syncthreads();
+  asm volatile("" : "+v"(id));   // consumed from here on: no wait for it ahead of the staging
+  Raw<D> zr, hr, xr;
+  if (has) fwd_out_a<D>(orr, Qr, T, wimg(w0), wimg(w1), lv, of, zr, hr, lane);
+  if constexpr (R::ON) {
+    __syncthreads();   // every wave is past the Wo and W1 GEMMs
+    stage_slot<D>(w0, Wk, D, wave, lane);
+    stage_slot<D>(w1, Wv, D, wave, lane);
+  }
+  asm volatile("" ::: "memory");   // no hoisting across the phases (registers)
+  if (has) {
+    fwd_out_b<D>(hr, zr, T, wimg(w2), lv, of, xr, lane, T.ok && id != 0);
+    asm volatile("" ::: "memory");
+    as_loaded<D>(xr);
+    fwd_in_q<D>(xr, T, wimg(w3), lv + 5 * D, b.eps, b.Q, b.mean, b.rstd, b.q, lane);
+  }
+  if constexpr (R::ON) __syncthreads();   // Wk, Wv have landed
+  asm volatile("" ::: "memory");
+  if (has) fwd_in_kv<D>(xr, T, wimg(R::ON ? w0 : w4), wimg(R::ON ? w1 : w5), lv + 5 * D, b.kv, lane);
+}
+
+// block i's block_in_bwd_kernel chain -> dx (registers only: never stored) -> block i-1's block_out_bwd_kernel chain.
+// red: block i's attention-LN partials, then block i-1's forward-LN partials (per workgroup, as the single kernels)
+template <int D>
+__global__ __launch_bounds__(NT) void block_in_out_bwd_kernel(InBwdArgs a, OutBwdArgs b) {
+  typedef Roll<D> R;
+  RC_BOUNDARY_SLOTS(D);
+  __shared__ __attribute__((aligned(16))) float lv[2 * D];   // ln1_w (block i) | ln2_w (block i-1)
+  __shared__ __attribute__((aligned(16))) float red[NW * 2 * D], red2[NW * 2 * D];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4,
+            cl = lane & 15;
+  const TileRange tr = tiles_of_wave(n_tiles(a.M), wave);
+  const bool has = tr.first < tr.end;   // this wave's one tile
+  const Tile T = tile_of(has ? tr.first : 0, a.M, cl);
+  const OutBwd ob = out_bwd_of(b);
+  Raw<D> kr, vr, qr, rr, xr;
+  float mu = 0.f, rs = 0.f;
+  int64_t id = 0;   // block i-1's mask id: requested with the first inputs (as block_out_in_kernel)
+  if (has) {
+    load_raw<D>(kr, a.dkv, 2 * D, T.mc, g);
+    load_raw<D>(vr, a.dkv + D, 2 * D, T.mc, g);
+    load_raw<D>(qr, a.dq, D, T.mc, g);
+    load_raw<D>(rr, a.dx1, D, T.mc, g);
+    load_raw<D>(xr, a.x, D, T.mc, g);
+    mu = a.mean1[T.mc];
+    rs = a.rstd1[T.mc];
+    id = b.ids[T.mc];
+  }
+  stage_slot<D>(w0, a.WinT + D, a.ldwt, wave, lane);       // Wk^T, Wv^T, Wq^T rows
+  stage_slot<D>(w1, a.WinT + 2 * D, a.ldwt, wave, lane);
+  stage_slot<D>(w2, a.WinT, a.ldwt, wave, lane);
+  stage_slot<D>(w3, b.W2T, D, wave, lane);
+  if constexpr (!R::ON) {
+    stage_slot<D>(w4, b.W1T, D, wave, lane);
+    stage_slot<D>(w5, b.WoT, D, wave, lane);
+  }
+  {
+    const float* const V[2] = {a.ln_w, b.ln_w};
+    stage_v<D, 2>(lv, V, tid);
+  }
+  ln_zero(red, D, lane, wave);
+  ln_zero(red2, D, lane, wave);
+  __syncthreads();
+  asm volatile("" : "+v"(id));   // consumed from here on: no wait for it ahead of the staging
+  Raw<D> dxkv, dxr, hr, x1r, orr, dzr, dar;
+  float mu2 = 0.f, rs2 = 0.f;
+  // bwd_in_a and bwd_in_b stay in ONE block of straight-line code, as in block_in_bwd_kernel: with the first barrier
+  // between them the compiler no longer saw dxkv's producer from bwd_in_b and paired / fused the LayerNorm backward's
+  // last expressions differently (dx off by a bf16 ulp in a few elements per million).  So the re-stage waits until
+  // this wave is done with all three phase-A images and runs under bwd_out_a alone.
+  if (has) {
+    bwd_in_a<D>(kr, vr, wimg(w0), wimg(w1), dxkv, lane);
+    // phase B's inputs go out before the re-stage and before the first store (vmcnt retires in order): they land
+    // under bwd_in_b, and the wait for them does not wait for the re-stage
+    load_raw<D>(hr, b.h1, D, T.mc, g);
+    load_raw<D>(x1r, b.x1, D, T.mc, g);
+    if (b.delta) load_raw<D>(orr, b.o, D, T.mc, g);
+    mu2 = b.mean2[T.mc];
+    rs2 = b.rstd2[T.mc];
+    bwd_in_b<D>(qr, rr, xr, dxkv, T, mu, rs, wimg(w2), lv, red, dxr, lane, wave);
+  }
+  if constexpr (R::ON) {
+    __syncthreads();   // every wave is past phase A's GEMMs
+    stage_slot<D>(w0, b.W1T, D, wave, lane);
+    stage_slot<D>(w1, b.WoT, D, wave, lane);
+  }
+  asm volatile("" ::: "memory");
+  if (has) {
+    as_loaded<D>(dxr);
+    bwd_out_a<D>(dxr, hr, T, wimg(w3), ob, dzr, dar, lane, T.ok && id != 0);
+  }
+  if constexpr (R::ON) __syncthreads();   // W1^T, Wo^T have landed
+  asm volatile("" ::: "memory");
+  if (has)
+    bwd_out_b<D>(dar, x1r, dzr, orr, T, mu2, rs2, wimg(R::ON ? w0 : w4), wimg(R::ON ? w1 : w5), lv + D, ob, red2,
+                 lane, wave);
+  ln_partials<D>(red, a.part, tid);
+  ln_partials<D>(red2, b.part, tid);
+}
+
 // ------------------------------------------------------------------ launch geometry
 static int g_ncu = 0;
 static int64_t grid_for(int64_t M) {
@@ -974,6 +1172,19 @@ static int launch_out(const OutArgs& a, int64_t d, void* stream) {
   else if (d == 128) head ? launch_out_t<128, true>(a, s) : launch_out_t<128, false>(a, s);
   else return RS_ERR_UNSUPPORTED;
   return (int)hipGetLastError();
+}
+
+// the boundary kernels' precondition: every wave of the grid owns at most one tile
+static bool boundary_fused(int64_t M, int64_t d) {
+  return M > 0 && (d == 64 || d == 128) && (M + TR - 1) / TR <= grid_for(M) * NW;
+}
+template <int D>
+static void launch_out_in_t(const OutArgs& a, const InArgs& b, hipStream_t s) {
+  hipLaunchKernelGGL(block_out_in_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, a, b);   // static LDS
+}
+template <int D>
+static void launch_in_out_bwd_t(const InBwdArgs& a, const OutBwdArgs& b, hipStream_t s) {
+  hipLaunchKernelGGL(block_in_out_bwd_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, a, b);
 }
 
 // ------------------------------------------------------------------ batched bf16 transpose
@@ -1139,6 +1350,60 @@ int rs_sas_block_in_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, c
   } else {
     return RS_ERR_UNSUPPORTED;
   }
+  return (int)hipGetLastError();
+}
+
+int rs_sas_block_boundary_fused(int64_t M, int64_t d) { return rc::boundary_fused(M, d) ? 1 : 0; }
+
+int rs_sas_block_out_in(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo, void* x1,
+                        const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
+                        const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
+                        const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2, const uint64_t* seed_base,
+                        const float* ln1_w, const float* ln1_b, float eps1, void* Qn, float* mean1, float* rstd1,
+                        const void* Wq, const float* bq, void* q, const void* Wkv, const float* bkv, void* kv,
+                        void* stream) {
+  if (M <= 0) return RS_ERR_ARG;
+  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
+  if (!rc::boundary_fused(M, d)) {
+    const int rc1 = rs_sas_block_out(M, d, o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn,
+                                     ids, drop_p, salt1, salt2, seed_base, stream);
+    if (rc1) return rc1;
+    return rs_sas_block_in(M, d, xn, d, ln1_w, ln1_b, eps1, Qn, mean1, rstd1, Wq, bq, q, Wkv, bkv, kv, stream);
+  }
+  rc::OutArgs a = {M, (const __bf16*)o, (const __bf16*)Q, (const __bf16*)Wo, bo, (__bf16*)x1, ln_w, ln_b, eps,
+                   (__bf16*)z, mean, rstd, (const __bf16*)W1, b1, (__bf16*)h1, (const __bf16*)W2, b2, (__bf16*)xn,
+                   ids, drop_p, salt1, salt2, seed_base};
+  rc::InArgs b = {M, (const __bf16*)xn, d, ln1_w, ln1_b, eps1, (__bf16*)Qn, mean1, rstd1, (const __bf16*)Wq, bq,
+                  (__bf16*)q, (const __bf16*)Wkv, bkv, (__bf16*)kv};
+  hipStream_t s = (hipStream_t)stream;
+  if (d == 64) rc::launch_out_in_t<64>(a, b, s);
+  else rc::launch_out_in_t<128>(a, b, s);
+  return (int)hipGetLastError();
+}
+
+int rs_sas_block_in_out_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
+                            const float* mean1, const float* rstd1, const float* ln1_w, const void* WinT, void* dx,
+                            float* part1, const int64_t* ids, const void* h1, const void* x1p, const float* mean2,
+                            const float* rstd2, const float* ln2_w, const void* W2T, const void* W1T, const void* WoT,
+                            void* dy2, void* da1, void* dx1p, void* dout, float* part2, float drop_p, uint64_t salt1,
+                            uint64_t salt2, const uint64_t* seed_base, const void* o, float* delta, void* stream) {
+  if (M <= 0 || !o != !delta) return RS_ERR_ARG;
+  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
+  if (!rc::boundary_fused(M, d)) {
+    if (!dx) return RS_ERR_ARG;
+    const int rc1 = rs_sas_block_in_bwd(M, d, dq, dkv, dx1, x, mean1, rstd1, ln1_w, WinT, dx, part1, stream);
+    if (rc1) return rc1;
+    return rs_sas_block_out_bwd_delta(M, d, dx, ids, h1, x1p, mean2, rstd2, ln2_w, W2T, W1T, WoT, dy2, da1, dx1p, dout,
+                                      part2, drop_p, salt1, salt2, seed_base, o, delta, stream);
+  }
+  rc::InBwdArgs a = {M, (const __bf16*)dq, (const __bf16*)dkv, (const __bf16*)dx1, (const __bf16*)x, mean1, rstd1,
+                     ln1_w, (const __bf16*)WinT, 3 * d, nullptr, part1};
+  rc::OutBwdArgs b = {M, nullptr, ids, (const __bf16*)h1, (const __bf16*)x1p, mean2, rstd2, ln2_w,
+                      (const __bf16*)W2T, (const __bf16*)W1T, (const __bf16*)WoT, (__bf16*)dy2, (__bf16*)da1,
+                      (__bf16*)dx1p, (__bf16*)dout, part2, drop_p, salt1, salt2, seed_base, (const __bf16*)o, delta};
+  hipStream_t s = (hipStream_t)stream;
+  if (d == 64) rc::launch_in_out_bwd_t<64>(a, b, s);
+  else rc::launch_in_out_bwd_t<128>(a, b, s);
   return (int)hipGetLastError();
 }
 

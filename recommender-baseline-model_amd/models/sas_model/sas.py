@@ -16,7 +16,8 @@ tiles through the sublayer chain in registers) around the LDS-resident attention
   x = (drop(relu(drop(z W1^T+b1)) W2^T+b2) + z)*m    (same launch)
   f = LN(x); pl/nl = <f, E[pos/neg]>; BCE + grads   rs_sas_block_out_head (the last block's output kernel)
 backward: rs_sas_block_out_bwd_delta -> rs_attn_bwd (dQ and dK/dV workgroups in one launch) ->
-rs_sas_block_in_bwd per block, then ONE grouped launch of every weight / bias / LayerNorm-affine gradient
+rs_sas_block_in_bwd per block (between two blocks one launch carries both adjacent row chains: rs_sas_block_out_in
+forward, rs_sas_block_in_out_bwd backward), then ONE grouped launch of every weight / bias / LayerNorm-affine gradient
 (rs_wgrad_grouped_pos_stats, with the positional table's gradient and the loss statistics) beside the item-table
 gradient by inverted index (rs_item_index_build on a side stream during the forward, rs_item_grad), then the fused
 Adam (rs_adam_prepare_step_loss).
@@ -219,6 +220,9 @@ class SASEngine:
         # so the forward's side branch builds only the item index and the backward needs no join for it
         self.adam_transposes = False
         self._wT = None
+        # the block-boundary launches (rs_sas_block_out_in, rs_sas_block_in_out_bwd: two adjacent row chains in one
+        # kernel); RS_SAS_BOUNDARY_FUSE=0 selects the composed launches they replace (A/B timing, bitwise tests)
+        self.boundary_fuse = os.environ.get("RS_SAS_BOUNDARY_FUSE", "1") != "0"
         salt0 = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.salt = {"emb": site_salt(salt0, 0)}
         for i in range(self.L):
@@ -413,13 +417,18 @@ class SASEngine:
             b = lay[i]
             ops.attn_fwd(B, T, H, Dh, b["q"], b["kv"][:, :d], b["kv"][:, d:], b["o"], b["lse"], 1.0 / math.sqrt(Dh),
                          0, ids, p, self.salt[f"attn{i}"], sb)
-            if head is not None and i == L - 1:
+            if i + 1 < L:
+                ln_w, ln_b, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv = in_args(i + 1)
+                if self.boundary_fuse:
+                    # this block's output chain and the next block's input chain in one launch (xn in registers)
+                    ops.sas_block_out_in(out_args(i), ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv)
+                else:
+                    ops.sas_block_out(*out_args(i))
+                    ops.sas_block_in(b["xn"], ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv)
+            elif head is not None:
                 ops.sas_block_out_head(out_args(i), *head)
             else:
                 ops.sas_block_out(*out_args(i))
-            if i + 1 < L:
-                ln_w, ln_b, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv = in_args(i + 1)
-                ops.sas_block_in(b["xn"], ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv)
             xs.append(b["xn"])
         for i in range(L):
             b = lay[i]
@@ -793,10 +802,16 @@ class SASEngine:
             ops.attn_bwd(B, T, H, Dh, s["q"][i], kv[:, :d], kv[:, d:], s["o"][i], g[i]["do"], s["lse"][i], dq,
                          dkv[:, :d], dkv[:, d:], 1.0 / math.sqrt(Dh), 0, ids, p, self.salt[f"attn{i}"], sb,
                          dl[i] if dl else wat, delta_in=bool(dl))
-            dxi = e("dxi", (M, d))
-            ops.sas_block_in_bwd(*in_bwd_args(i), dxi, lnp[i, 1])
-            if i > 0:
-                ops.sas_block_out_bwd(dxi, *out_bwd_args(i - 1))
+            if i > 0 and self.boundary_fuse:
+                # this block's input-side backward and the previous block's output-side backward in one launch: the
+                # gradient between them stays in registers (a scratch only where the entry runs two launches)
+                dxi = None if ops.sas_block_boundary_fused(M, d) else e("dxi", (M, d))
+                ops.sas_block_in_out_bwd(in_bwd_args(i), dxi, lnp[i, 1], out_bwd_args(i - 1))
+            else:
+                dxi = e("dxi", (M, d))
+                ops.sas_block_in_bwd(*in_bwd_args(i), dxi, lnp[i, 1])
+                if i > 0:
+                    ops.sas_block_out_bwd(dxi, *out_bwd_args(i - 1))
             dx = dxi
             Gin, Gb = G(pre + "in_proj_weight"), G(pre + "in_proj_bias")
             probs += [(g[i]["dy2"], s["h1"][i], G(fw + "conv2.weight"), G(fw + "conv2.bias")),

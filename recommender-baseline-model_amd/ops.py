@@ -578,6 +578,38 @@ def sas_block_in_bwd(dq, dkv, dx1, x, mean1, rstd1, ln_w, WinT, dx, part):
          ptr(WinT), ptr(dx), ptr(part), stream())
 
 
+def sas_block_boundary_fused(M, d):
+    """True where the block-boundary entries below run their one-launch kernels (every wave owns at most one
+    tile); they launch the two single-block kernels otherwise."""
+    return bool(_lib.lib().rs_sas_block_boundary_fused(M, d))
+
+
+def sas_block_out_in(out_args, ln1_w, ln1_b, eps1, Qn, mean1, rstd1, Wq, bq, q, Wkv, bkv, kv):
+    """sas_block_out(*out_args) of block i, then sas_block_in(xn, ...) of block i+1 on the tile in registers: one
+    launch (rowchain), bitwise the two calls' results."""
+    (o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
+     seed_base) = out_args
+    M, d = o.shape
+    call("rs_sas_block_out_in", M, d, ptr(o), ptr(Q), ptr(Wo), ptr(bo), ptr(x1), ptr(ln_w), ptr(ln_b), eps, ptr(z),
+         ptr(mean), ptr(rstd), ptr(W1), ptr(b1), ptr(h1), ptr(W2), ptr(b2), ptr(xn), ptr(ids), drop_p, salt1, salt2,
+         ptr(seed_base), ptr(ln1_w), ptr(ln1_b), eps1, ptr(Qn), ptr(mean1), ptr(rstd1), ptr(Wq), ptr(bq), ptr(q),
+         ptr(Wkv), ptr(bkv), ptr(kv), stream())
+
+
+def sas_block_in_out_bwd(in_args, dx, part1, out_args):
+    """sas_block_in_bwd(*in_args, dx, part1) of block i, then sas_block_out_bwd(dx, *out_args) of block i-1 on the
+    tile in registers: one launch (rowchain), bitwise the two calls' results except that dx is not written.  dx: the
+    scratch of the two-launch path, None allowed where sas_block_boundary_fused(M, d)."""
+    dq, dkv, dx1, x, mean1, rstd1, ln1_w, WinT = in_args
+    (ids, h1, x1, mean2, rstd2, ln2_w, W2T, W1T, WoT, dy2, da1, dx1o, dout, part2, drop_p, salt1, salt2,
+     seed_base, o, delta) = out_args
+    M, d = dq.shape
+    call("rs_sas_block_in_out_bwd", M, d, ptr(dq), ptr(dkv), ptr(dx1), ptr(x), ptr(mean1), ptr(rstd1), ptr(ln1_w),
+         ptr(WinT), ptr(dx), ptr(part1), ptr(ids), ptr(h1), ptr(x1), ptr(mean2), ptr(rstd2), ptr(ln2_w), ptr(W2T),
+         ptr(W1T), ptr(WoT), ptr(dy2), ptr(da1), ptr(dx1o), ptr(dout), ptr(part2), drop_p, salt1, salt2,
+         ptr(seed_base), ptr(o), ptr(delta), stream())
+
+
 # ---- union-of-touched-rows table-gradient exchange (sparse_rows.hip) -------------------------
 def touched_rows_ws_numel(rows):
     return int(_lib.lib().rs_touched_rows_ws_numel(rows))

@@ -200,6 +200,15 @@ def main():
         dqkv = rn(M, 2 * d)
         run("fused block_in_bwd", lambda: ops.sas_block_in_bwd(qq, dqkv, dx1, x, m1_, r1_, gam, WinT, z, part),
             6 * mb)
+        # the block-boundary launches: block_out + block_in / block_in_bwd + block_out_bwd in one kernel each
+        run("fused block_out_in", lambda: ops.sas_block_out_in(
+            (oo, Q, W, bias, x1, gam, bet, 1e-8, zz, m1_, r1_, W, bias, h1, W, bias, xn, ids, a.drop, 3, 4, sb),
+            gam, bet, 1e-8, Q, m1_, r1_, Win[:d], bin_[:d], qq, Win[d:], bin_[d:], kvb), 11 * mb)
+        part2 = torch.empty_like(part)
+        run("fused block_in_out_bwd", lambda: ops.sas_block_in_out_bwd(
+            (qq, dqkv, dx1, x, m1_, r1_, gam, WinT), z, part,
+            (ids, h1, x1, m1_, r1_, gam, WT, WT, WT, dy2, da1, dx1, do_, part2, a.drop, 3, 4, sb, None, None)),
+            12 * mb)
         probs = []
         for _ in range(2):
             probs += [(dy2, h1, torch.zeros(d, d, device=dev), torch.zeros(d, device=dev)),
