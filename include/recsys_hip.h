@@ -515,6 +515,25 @@ int rs_sas_block_in_out_bwd(int64_t M, int64_t d, const void* dq, const void* dk
                             const float* rstd2, const float* ln2_w, const void* W2T, const void* W1T, const void* WoT,
                             void* dy2, void* da1, void* dx1o, void* dout, float* part2, float drop_p, uint64_t salt1,
                             uint64_t salt2, const uint64_t* seed_base, const void* o, float* delta, void* stream);
+/* The forward/backward turnaround of the fused training step (rowchain.hip): rs_sas_block_out_head of the LAST block
+ * and, on the same rows, that block's rs_sas_block_out_bwd_delta(dxn = dx, h1, x1, mean2 = mean, rstd2 = rstd, ln_w,
+ * o) in ONE launch: dx_L, h1, x1, o and the row statistics pass from the forward chain to the backward chain in
+ * registers.  Results are bitwise those of the two entries called back to back, for every M: the one-launch kernel
+ * runs where rs_sas_block_boundary_fused(M, d), the two kernels are launched on the stream otherwise.  Every output
+ * of either entry is written (x1, mean, rstd, xn included) except dx, which the one-launch kernel does NOT write: it
+ * is the two-launch path's scratch and may be NULL when rs_sas_block_boundary_fused(M, d) (RS_ERR_ARG if it is NULL
+ * and needed).  W2T / W1T / WoT: the block's transposed weights (they must be current when the launch runs);
+ * part2: the forward-LN partials (rs_sas_block_out_bwd's part); delta: optional, rowsum(dout * o).
+ * Error codes as rs_sas_block_out_head. */
+int rs_sas_block_out_head_bwd(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo,
+                              void* x1, const float* ln_w, const float* ln_b, float eps, void* z, float* mean,
+                              float* rstd, const void* W1, const float* b1, void* h1, const void* W2, const float* b2,
+                              void* xn, const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2,
+                              const uint64_t* seed_base, const void* E, const int64_t* pos, const int64_t* neg,
+                              const float* lnl_w, const float* lnl_b, const int* count_parts, int64_t ncount,
+                              const float* divisor, void* f, float* pl, float* nl, float* dpl, float* dnl, void* dx,
+                              float* lnpart, float* part, const void* W2T, const void* W1T, const void* WoT, void* dy2,
+                              void* da1, void* dx1, void* dout, float* part2, float* delta, void* stream);
 /* Batched bf16 transpose: for m < nmat, desc[6m..6m+5] = {rows, cols, src_off, lds, dst_off, ldd}
  * (elements): dst[dst_off + c*ldd + r] = src[src_off + r*lds + c].  Grid x = max_tiles >= the
  * largest ceil(rows/64)*ceil(cols/64). */

@@ -196,6 +196,52 @@ __device__ __forceinline__ void ln_fwd(Act<D>& x, const float* gw, const float* 
   }
 }
 
+// ln_fwd with the sum of squares spelled out operation by operation, for the turnaround kernel's head.  In
+// block_out_kernel<D, true> the head's LayerNorm is compiled together with fwd_out_b's epilogue, and there the
+// compiler fuses u*u into the running sum for features 8k and 8k + 1 of the lane (k > 0; feature 0's onto feature 1's
+// square) and multiplies, then adds, for the others.  Which squares it fuses follows from how it vectorized the code
+// before them, differs in every kernel that inlines the stage (a straight-line kernel fused the even features: rstd
+// 1 ulp apart, f and dx_L a bf16 ulp apart in a few elements per million), and decides rstd's last bit.  This form
+// computes block_out_kernel<D, true>'s sequence whatever surrounds it (held bitwise by
+// tests/test_rowchain_turnaround_gpu.py; the mean, the division and the affine part round the same in either form).
+template <int D>
+__device__ __forceinline__ void ln_fwd_head(Act<D>& x, const float* gw, const float* gb, float eps, int g, float& mu,
+                                            float& rs) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < Lay<D>::J; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += x.v[j][e];
+  mu = row_sum(s) / (float)D;
+  float q = 0.f, u0 = 0.f;
+#pragma unroll
+  for (int j = 0; j < Lay<D>::J; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float u = x.v[j][e] - mu;
+      if (j == 0 && e == 0) {
+        u0 = u;
+      } else if (j == 0 && e == 1) {
+        float sq = u * u;
+        asm volatile("" : "+v"(sq));
+        q = __builtin_fmaf(u0, u0, sq);   // the first two: feature 0's square fused onto feature 1's
+      } else if ((j & 1) == 0 && e < 2) {
+        q = __builtin_fmaf(u, u, q);
+      } else {
+        float sq = u * u;
+        asm volatile("" : "+v"(sq));   // a product of its own: no fusing into the sum
+        q += sq;
+      }
+    }
+  rs = 1.0f / sqrtf(row_sum(q) / (float)D + eps);
+#pragma unroll
+  for (int j = 0; j < Lay<D>::J; ++j) {
+    const f32x4 w = vec4<D>(gw, j, g), b = vec4<D>(gb, j, g);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x.v[j][e] = (x.v[j][e] - mu) * rs * w[e] + b[e];
+  }
+}
+
 // sum over the 16 lanes of a DPP row (the 16 tokens of a lane group): common.h row16_sum_up, the xor butterfly's
 // bits from DPP operand moves instead of __shfl_xor's ds_bpermute_b32 (~260 LDS-crossbar round trips per tile in the
 // LayerNorm backwards).  Every caller runs with all 64 lanes active (wave-uniform tile loops).
@@ -205,7 +251,10 @@ __device__ __forceinline__ float row16_sum(float v) { return row16_sum_up(v); }
 // - rstd^3*mean(dy*g*u)*u, u = x - mean (x as stored, bf16); dy zeroed on invalid tokens.  The dgamma/dbeta
 // terms of the tile's 16 tokens are summed by an xor tree over the lanes of a group as they are formed and added
 // to the wave's own LDS row red[wave][2][D] (no other wave touches it before ln_partials' barrier)
-template <int D>
+// HEAD_FORM (the turnaround kernel's head, see ln_fwd_head): the sums of dy*g and dy*g*u with every product fused into
+// the sum, as block_out_kernel<D, true> has it (the straight-line kernel multiplied in pairs and added: dx_L a bf16 ulp apart
+// in a few elements per hundred thousand), and the last expression's products as it rounds them
+template <int D, bool HEAD_FORM = false>
 __device__ __forceinline__ void ln_bwd(Act<D>& dy, const Raw<D>& xr, bool valid, const float* gw, float mu, float a,
                                        float* red, int lane, int wave) {
   const int g = lane >> 4, cl = lane & 15;
@@ -224,8 +273,13 @@ __device__ __forceinline__ void ln_bwd(Act<D>& dy, const Raw<D>& xr, bool valid,
         rw[feat(j, g, e)] += pg;
         rw[D + feat(j, g, e)] += pb;
       }
-      sg += gq;
-      sgu += gq * u;
+      if constexpr (HEAD_FORM) {
+        sg = __builtin_fmaf(gy, w[e], sg);   // the unrounded dy*g, although gq is also formed
+        sgu = __builtin_fmaf(u, gq, sgu);
+      } else {
+        sg += gq;
+        sgu += gq * u;
+      }
       dy.v[j][e] = gq;   // dy*g for now
     }
   }
@@ -240,8 +294,23 @@ __device__ __forceinline__ void ln_bwd(Act<D>& dy, const Raw<D>& xr, bool valid,
 #pragma unroll
   for (int j = 0; j < Lay<D>::J; ++j)
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
-      dy.v[j][e] = a * (dy.v[j][e] - mg) - coef * ((float)xr.v[j >> 1][4 * (j & 1) + e] - mu);
+    for (int e = 0; e < 4; ++e) {
+      const float u = (float)xr.v[j >> 1][4 * (j & 1) + e] - mu;
+      if constexpr (HEAD_FORM) {
+        // block_out_kernel<D, true>'s form: both products rounded for features 8k and 8k + 1 of the lane, the first
+        // one fused into the subtraction for the others
+        float p1 = a * (dy.v[j][e] - mg), p2 = coef * u;
+        if ((j & 1) == 0 && e < 2) {
+          asm volatile("" : "+v"(p1), "+v"(p2));
+          dy.v[j][e] = p1 - p2;
+        } else {
+          asm volatile("" : "+v"(p2));
+          dy.v[j][e] = __builtin_fmaf(a, dy.v[j][e] - mg, -p2);
+        }
+      } else {
+        dy.v[j][e] = a * (dy.v[j][e] - mg) - coef * u;
+      }
+    }
 }
 
 __device__ __forceinline__ void ln_zero(float* red, int D, int lane, int wave) {
@@ -364,13 +433,13 @@ __device__ __forceinline__ void drop4(float p, uint32_t s32, int64_t m, int D, i
 }
 // Forward, block output side part 1 (sas.py:75-80): x1 = Q + o Wo^T + bo [saved], z = LN2(x1) [saved],
 // h1 = relu(drop(z W1^T + b1)) [saved].  lv: bo, ln2_w, ln2_b, b1, b2.
+// (fwd_out_a_x also hands back the rounded x1 and the row statistics: the turnaround kernel's backward reads them)
 template <int D>
-__device__ __forceinline__ void fwd_out_a(const Raw<D>& orr, const Raw<D>& Qr, const Tile& T, const bf16* wo,
-                                          const bf16* w1, const float* lv, const OutFwd& o, Raw<D>& zr, Raw<D>& hr,
-                                          int lane) {
+__device__ __forceinline__ void fwd_out_a_x(const Raw<D>& orr, const Raw<D>& Qr, const Tile& T, const bf16* wo,
+                                            const bf16* w1, const float* lv, const OutFwd& o, Raw<D>& zr, Raw<D>& hr,
+                                            int lane, Raw<D>& r, float& mu, float& rs) {
   const int g = lane >> 4;
   Act<D> acc;
-  Raw<D> r;
   zero<D>(acc);
   mm<D>(wo, orr, acc, lane);
 #pragma unroll
@@ -381,7 +450,6 @@ __device__ __forceinline__ void fwd_out_a(const Raw<D>& orr, const Raw<D>& Qr, c
   }
   round_act<D>(acc, r);
   if (!RC_NOSTORE) store_raw<D>(o.x1, D, T.m, T.ok, r, g);
-  float mu, rs;
   ln_fwd<D>(acc, lv + D, lv + 2 * D, o.eps, g, mu, rs);
   round_act<D>(acc, zr);
   if (!RC_NOSTORE) store_raw<D>(o.z, D, T.m, T.ok, zr, g);
@@ -402,6 +470,14 @@ __device__ __forceinline__ void fwd_out_a(const Raw<D>& orr, const Raw<D>& Qr, c
   }
   round_act<D>(acc, hr);
   if (!RC_NOSTORE) store_raw<D>(o.h1, D, T.m, T.ok, hr, g);
+}
+template <int D>
+__device__ __forceinline__ void fwd_out_a(const Raw<D>& orr, const Raw<D>& Qr, const Tile& T, const bf16* wo,
+                                          const bf16* w1, const float* lv, const OutFwd& o, Raw<D>& zr, Raw<D>& hr,
+                                          int lane) {
+  Raw<D> r;
+  float mu, rs;
+  fwd_out_a_x<D>(orr, Qr, T, wo, w1, lv, o, zr, hr, lane, r, mu, rs);
 }
 // part 2 (sas.py:81-84): x' = (drop(h1 W2^T + b2) + z) * (ids != 0) [saved] -> xr
 // (keep = T.ok && ids[T.mc] != 0: given by a caller that has requested the id earlier)
@@ -685,15 +761,19 @@ __device__ __forceinline__ void head_rows_at(const HeadArgs& h, int64_t ip, int6
   load_raw<D>(er, h.E, D, ip, g);
   load_raw<D>(nr, h.E, D, in, g);
 }
-template <int D>
-__device__ __forceinline__ void head_tile(const Raw<D>& xr, const Raw<D>& er, const Raw<D>& nr, int64_t ip,
-                                          const Tile& T, const float* gl, const float* bl, const HeadArgs& h,
-                                          float scale, float* red, float (&acc)[3], int lane, int wave) {
+// (head_tile_x hands dx_L back, rounded as stored; STORE_DX false: the turnaround kernel -- dx_L in registers only,
+// and the LayerNorm in the form that does not depend on the kernel around it, ln_fwd_head)
+template <int D, bool STORE_DX>
+__device__ __forceinline__ void head_tile_x(const Raw<D>& xr, const Raw<D>& er, const Raw<D>& nr, int64_t ip,
+                                            const Tile& T, const float* gl, const float* bl, const HeadArgs& h,
+                                            float scale, float* red, float (&acc)[3], int lane, int wave,
+                                            Raw<D>& dxr) {
   const int g = lane >> 4;
   Act<D> y;
   to_act<D>(y, xr);
   float mu, rs;
-  ln_fwd<D>(y, gl, bl, h.eps, g, mu, rs);
+  if constexpr (STORE_DX) ln_fwd<D>(y, gl, bl, h.eps, g, mu, rs);
+  else ln_fwd_head<D>(y, gl, bl, h.eps, g, mu, rs);
   Raw<D> fr;
   round_act<D>(y, fr);                       // the logits read the stored (bf16) features
   store_raw<D>(h.f, D, T.m, T.ok, fr, g);
@@ -727,10 +807,18 @@ __device__ __forceinline__ void head_tile(const Raw<D>& xr, const Raw<D>& er, co
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       df.v[j][e] = gp * (float)er.v[j >> 1][4 * (j & 1) + e] + gn * (float)nr.v[j >> 1][4 * (j & 1) + e];
-  ln_bwd<D>(df, xr, T.ok, gl, mu, rs, red, lane, wave);
+  ln_bwd<D, !STORE_DX>(df, xr, T.ok, gl, mu, rs, red, lane, wave);
   Raw<D> dr;
   round_act<D>(df, dr);
-  store_raw<D>(h.dx, D, T.m, T.ok, dr, g);
+  if (STORE_DX) store_raw<D>(h.dx, D, T.m, T.ok, dr, g);
+  dxr = dr;
+}
+template <int D>
+__device__ __forceinline__ void head_tile(const Raw<D>& xr, const Raw<D>& er, const Raw<D>& nr, int64_t ip,
+                                          const Tile& T, const float* gl, const float* bl, const HeadArgs& h,
+                                          float scale, float* red, float (&acc)[3], int lane, int wave) {
+  Raw<D> dr;
+  head_tile_x<D, true>(xr, er, nr, ip, T, gl, bl, h, scale, red, acc, lane, wave, dr);
 }
 __device__ __forceinline__ OutFwd out_fwd_of(const OutArgs& a) {
   const bool drop = a.drop_p > 0.f;
@@ -1134,6 +1222,141 @@ __global__ __launch_bounds__(NT) void block_in_out_bwd_kernel(InBwdArgs a, OutBw
   ln_partials<D>(red2, b.part, tid);
 }
 
+// The forward/backward turnaround: the LAST block's block_out_kernel<D, true> chain (output side, last LayerNorm,
+// sampled head, BCE gradient, the last LayerNorm's backward) -> dx_L, h1, x1, o, mean2, rstd2 (registers: dx_L is never
+// stored, the others are stored for the later launches as before) -> the same block's block_out_bwd_kernel chain.
+// The two launches it replaces are adjacent on the main queue and deal the same rows to the same waves.
+// Images: Wo, W1, W2 | W2^T, W1^T, Wo^T; at D = 128 slots 0 and 1 are re-staged with W1^T, Wo^T once every wave is
+// past fwd_out_a, and that LDS-DMA runs under fwd_out_b, the whole head and bwd_out_a.
+// red: the last LayerNorm's partials (a.h.lnpart), red2: the block's forward-LN partials (b.part).
+//
+// The two argument sets hold 41 pointers, more than the scalar registers hold at once: the compiler reads every
+// kernel argument at the kernel's entry and would park the backward's in spare vector lanes until their use.  So the
+// arguments are ONE struct, and the backward's late ones (W1^T, Wo^T for the re-stage; the output pointers) are read
+// from the kernel-argument segment where they are first needed, through a pointer the optimizer cannot see through.
+// Of b only those and W2T are read: the rest (rows, ids, seeds, the saved tensors) are a's.
+struct TurnArgs {
+  OutArgs a;
+  OutBwdArgs b;
+};
+typedef const __attribute__((address_space(4))) TurnArgs* TurnArgsPtr;
+__device__ __forceinline__ TurnArgsPtr turn_args_late() {
+  TurnArgsPtr kp = (TurnArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();   // explicit arguments start at offset 0
+  asm volatile("" : "+s"(kp));
+  return kp;
+}
+template <int D>
+__global__ __launch_bounds__(NT) void block_out_head_bwd_kernel(TurnArgs k) {
+  const OutArgs& a = k.a;
+  typedef Roll<D> R;
+  RC_BOUNDARY_SLOTS(D);
+  __shared__ __attribute__((aligned(16))) float lv[7 * D];   // bo, ln2_w, ln2_b, b1, b2 | gl, bl
+  __shared__ __attribute__((aligned(16))) float red[NW * 2 * D], red2[NW * 2 * D];
+  __shared__ float hred[4][NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4,
+            cl = lane & 15;
+  RCPROF(0);
+  const TileRange tr = tiles_of_wave(n_tiles(a.M), wave);
+  const bool has = tr.first < tr.end;   // this wave's one tile
+  const Tile T = tile_of(has ? tr.first : 0, a.M, cl);
+  const OutFwd of = out_fwd_of(a);
+  // every index the chain needs is requested with the first inputs: a load issued after the first store or after the
+  // re-stage would be waited for together with it (vmcnt retires in order and counts stores)
+  Raw<D> orr, Qr;
+  int64_t id = 0, ip = 0, in = 0;
+  if (has) {
+    load_raw<D>(orr, a.o, D, T.mc, g);
+    load_raw<D>(Qr, a.Q, D, T.mc, g);
+    id = a.ids[T.mc];
+    ip = a.h.pos[T.mc];
+    in = a.h.neg[T.mc];
+  }
+  stage_slot<D>(w0, a.Wo, D, wave, lane);
+  stage_slot<D>(w1, a.W1, D, wave, lane);
+  stage_slot<D>(w2, a.W2, D, wave, lane);
+  stage_slot<D>(w3, k.b.W2T, D, wave, lane);
+  if constexpr (!R::ON) {
+    stage_slot<D>(w4, k.b.W1T, D, wave, lane);
+    stage_slot<D>(w5, k.b.WoT, D, wave, lane);
+  }
+  {
+    const float* const V[7] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2, a.h.gl, a.h.bl};
+    stage_v<D, 7>(lv, V, tid);
+  }
+  ln_zero(red, D, lane, wave);
+  ln_zero(red2, D, lane, wave);
+  // the loss's divisor, as block_out_kernel forms it
+  float hacc[3] = {0.f, 0.f, 0.f};
+  {
+    int c = 0;
+    for (int i = tid; i < a.h.ncnt; i += NT) c += a.h.cnt_parts[i];
+    c = (int)wave_sum((float)c);   // exact: counts < 2^24
+    if (lane == 0) hred[3][wave] = (float)c;
+  }
+  __syncthreads();
+  float hscale;
+  {
+    float c = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) c += hred[3][w];
+    hscale = 1.f / (a.h.divisor ? *a.h.divisor : c);
+  }
+  asm volatile("" : "+v"(id), "+v"(ip), "+v"(in));   // consumed from here on: no wait for them ahead of the staging
+  RCPROF(1);
+  Raw<D> zr, hr, x1r, xr, er, nr, dr, dzr, dar;
+  float mu2 = 0.f, rs2 = 0.f;
+  if (has) {
+    fwd_out_a_x<D>(orr, Qr, T, wimg(w0), wimg(w1), lv, of, zr, hr, lane, x1r, mu2, rs2);
+    head_rows_at<D>(a.h, ip, in, er, nr, g);   // ahead of the re-stage; they land under fwd_out_b
+  }
+  RCPROF(2);
+  if constexpr (R::ON) {
+    __syncthreads();   // every wave is past the Wo and W1 GEMMs
+    const TurnArgsPtr kp = turn_args_late();
+    stage_slot<D>(w0, kp->b.W1T, D, wave, lane);
+    stage_slot<D>(w1, kp->b.WoT, D, wave, lane);
+  }
+  asm volatile("" ::: "memory");   // no hoisting across the phases (registers)
+  const TurnArgsPtr kb = turn_args_late();
+  const OutBwd ob = {kb->b.dy2, kb->b.da1, kb->b.dx1, kb->b.dout, kb->b.delta, a.ids, a.drop_p, of.s1, of.s2};
+  if (has) {
+    const bool keep = T.ok && id != 0;
+    fwd_out_b<D>(hr, zr, T, wimg(w2), lv, of, xr, lane, keep);
+    RCPROF(4);
+    head_tile_x<D, false>(xr, er, nr, ip, T, lv + 5 * D, lv + 6 * D, a.h, hscale, red, hacc, lane, wave, dr);
+    RCPROF(6);
+    asm volatile("" ::: "memory");
+    // the backward sees what block_out_bwd_kernel sees after its loads: opaque rounded values
+    as_loaded<D>(dr);
+    as_loaded<D>(hr);
+    bwd_out_a<D>(dr, hr, T, wimg(w3), ob, dzr, dar, lane, keep);
+  }
+  if constexpr (R::ON) __syncthreads();   // W1^T, Wo^T have landed
+  asm volatile("" ::: "memory");
+  if (has) {
+    as_loaded<D>(x1r);
+    as_loaded<D>(orr);
+    asm volatile("" : "+v"(mu2), "+v"(rs2));
+    bwd_out_b<D>(dar, x1r, dzr, orr, T, mu2, rs2, wimg(R::ON ? w0 : w4), wimg(R::ON ? w1 : w5), lv + D, ob, red2, lane,
+                 wave);
+  }
+  RCPROF(5);
+  // BCE partials: lanes -> waves -> the workgroup's row (fixed order); both LN affine partial sets likewise
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float v = wave_sum(hacc[k]);
+    if (lane == 0) hred[k][wave] = v;
+  }
+  ln_partials<D>(red, a.h.lnpart, tid);   // begins with a barrier
+  ln_partials<D>(red2, kb->b.part, tid);
+  if (tid < 3) {
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += hred[tid][w];
+    a.h.part[blockIdx.x * 3 + tid] = v;
+  }
+}
+
 // ------------------------------------------------------------------ launch geometry
 static int g_ncu = 0;
 static int64_t grid_for(int64_t M) {
@@ -1185,6 +1408,10 @@ static void launch_out_in_t(const OutArgs& a, const InArgs& b, hipStream_t s) {
 template <int D>
 static void launch_in_out_bwd_t(const InBwdArgs& a, const OutBwdArgs& b, hipStream_t s) {
   hipLaunchKernelGGL(block_in_out_bwd_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, a, b);
+}
+template <int D>
+static void launch_out_head_bwd_t(const OutArgs& a, const OutBwdArgs& b, hipStream_t s) {
+  hipLaunchKernelGGL(block_out_head_bwd_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, TurnArgs{a, b});
 }
 
 // ------------------------------------------------------------------ batched bf16 transpose
@@ -1404,6 +1631,40 @@ int rs_sas_block_in_out_bwd(int64_t M, int64_t d, const void* dq, const void* dk
   hipStream_t s = (hipStream_t)stream;
   if (d == 64) rc::launch_in_out_bwd_t<64>(a, b, s);
   else rc::launch_in_out_bwd_t<128>(a, b, s);
+  return (int)hipGetLastError();
+}
+
+int rs_sas_block_out_head_bwd(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo,
+                              void* x1, const float* ln_w, const float* ln_b, float eps, void* z, float* mean,
+                              float* rstd, const void* W1, const float* b1, void* h1, const void* W2, const float* b2,
+                              void* xn, const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2,
+                              const uint64_t* seed_base, const void* E, const int64_t* pos, const int64_t* neg,
+                              const float* lnl_w, const float* lnl_b, const int* count_parts, int64_t ncount,
+                              const float* divisor, void* f, float* pl, float* nl, float* dpl, float* dnl, void* dx,
+                              float* lnpart, float* part, const void* W2T, const void* W1T, const void* WoT, void* dy2,
+                              void* da1, void* dx1, void* dout, float* part2, float* delta, void* stream) {
+  if (M <= 0 || !E || !pos || !neg || !count_parts || ncount <= 0 || !f || !lnpart || !part) return RS_ERR_ARG;
+  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
+  if (!rc::boundary_fused(M, d)) {
+    if (!dx) return RS_ERR_ARG;
+    const int rc1 = rs_sas_block_out_head(M, d, o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn,
+                                          ids, drop_p, salt1, salt2, seed_base, E, pos, neg, lnl_w, lnl_b, count_parts,
+                                          ncount, divisor, f, pl, nl, dpl, dnl, dx, lnpart, part, stream);
+    if (rc1) return rc1;
+    return rs_sas_block_out_bwd_delta(M, d, dx, ids, h1, x1, mean, rstd, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout,
+                                      part2, drop_p, salt1, salt2, seed_base, delta ? o : nullptr, delta, stream);
+  }
+  rc::OutArgs a = {M, (const __bf16*)o, (const __bf16*)Q, (const __bf16*)Wo, bo, (__bf16*)x1, ln_w, ln_b, eps,
+                   (__bf16*)z, mean, rstd, (const __bf16*)W1, b1, (__bf16*)h1, (const __bf16*)W2, b2, (__bf16*)xn,
+                   ids, drop_p, salt1, salt2, seed_base,
+                   rc::HeadArgs{(const __bf16*)E, pos, neg, lnl_w, lnl_b, eps, count_parts, (int)ncount, divisor,
+                                (__bf16*)f, pl, nl, dpl, dnl, nullptr, lnpart, part}};
+  rc::OutBwdArgs b = {M, nullptr, ids, (const __bf16*)h1, (const __bf16*)x1, mean, rstd, ln_w, (const __bf16*)W2T,
+                      (const __bf16*)W1T, (const __bf16*)WoT, (__bf16*)dy2, (__bf16*)da1, (__bf16*)dx1, (__bf16*)dout,
+                      part2, drop_p, salt1, salt2, seed_base, (const __bf16*)o, delta};
+  hipStream_t s = (hipStream_t)stream;
+  if (d == 64) rc::launch_out_head_bwd_t<64>(a, b, s);
+  else rc::launch_out_head_bwd_t<128>(a, b, s);
   return (int)hipGetLastError();
 }
 

@@ -17,7 +17,9 @@ tiles through the sublayer chain in registers) around the LDS-resident attention
   f = LN(x); pl/nl = <f, E[pos/neg]>; BCE + grads   rs_sas_block_out_head (the last block's output kernel)
 backward: rs_sas_block_out_bwd_delta -> rs_attn_bwd (dQ and dK/dV workgroups in one launch) ->
 rs_sas_block_in_bwd per block (between two blocks one launch carries both adjacent row chains: rs_sas_block_out_in
-forward, rs_sas_block_in_out_bwd backward), then ONE grouped launch of every weight / bias / LayerNorm-affine gradient
+forward, rs_sas_block_in_out_bwd backward; in the fused training step the last block's output chain, the head and
+that block's output-side backward are one launch too: rs_sas_block_out_head_bwd), then ONE grouped launch of every
+weight / bias / LayerNorm-affine gradient
 (rs_wgrad_grouped_pos_stats, with the positional table's gradient and the loss statistics) beside the item-table
 gradient by inverted index (rs_item_index_build on a side stream during the forward, rs_item_grad), then the fused
 Adam (rs_adam_prepare_step_loss).
@@ -223,6 +225,9 @@ class SASEngine:
         # the block-boundary launches (rs_sas_block_out_in, rs_sas_block_in_out_bwd: two adjacent row chains in one
         # kernel); RS_SAS_BOUNDARY_FUSE=0 selects the composed launches they replace (A/B timing, bitwise tests)
         self.boundary_fuse = os.environ.get("RS_SAS_BOUNDARY_FUSE", "1") != "0"
+        # the forward/backward turnaround launch (rs_sas_block_out_head_bwd: the last block's output chain, the head
+        # and that block's output-side backward in one kernel); RS_SAS_TURNAROUND_FUSE=0 selects the two launches
+        self.turnaround_fuse = os.environ.get("RS_SAS_TURNAROUND_FUSE", "1") != "0"
         salt0 = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.salt = {"emb": site_salt(salt0, 0)}
         for i in range(self.L):
@@ -425,6 +430,16 @@ class SASEngine:
                 else:
                     ops.sas_block_out(*out_args(i))
                     ops.sas_block_in(b["xn"], ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv)
+            elif head is not None and self.turnaround_fuse:
+                # the fused training step: the backward is known to follow, and its first launch (this block's
+                # output-side backward) is a row chain on the rows this launch holds -- one launch for both
+                if self._side_refreshed:
+                    # the side branch writes the transposed weights during this forward (otherwise the previous
+                    # step's optimizer wrote them)
+                    torch.cuda.current_stream().wait_event(s["side"][0])
+                tb = self._out_bwd_bufs(s, i)
+                ops.sas_block_out_head_bwd(out_args(i), head, *tb["args"])
+                s["turnaround"] = tb
             elif head is not None:
                 ops.sas_block_out_head(out_args(i), *head)
             else:
@@ -468,6 +483,7 @@ class SASEngine:
             E, gl = self.W("item_emb.weight"), self.Wf("last_layernorm.weight")
             stats = ()
             nb = -(-M // 64)
+            assert dpl is None or "turnaround" not in s, "the forward already ran the backward of its own BCE gradient"
             if dpl is None and "head_in_block" in s:
                 # the head ran inside the last block's output kernel (forward)
                 assert s["hdiv"] is divisor, "backward's divisor must be the one forward's head used"
@@ -761,6 +777,19 @@ class SASEngine:
         ops.transpose_bf16(self._wT_desc, self._wT_tiles, self.flat.bf16, self._wT)
         return self._wT
 
+    def _out_bwd_bufs(self, s, i):
+        """Block i's output-side backward issued from the forward (the turnaround launch): its gradient buffers,
+        and the arguments of ops.sas_block_out_head_bwd after the head's (the workspaces are those
+        _backward_blocks_fused uses)."""
+        B, T = s["B"], s["T"]
+        M, d, H, L = B * T, self.d, self.H, self.L
+        e = self._buf
+        wT = self._wT.view(L, 6, d, d)
+        lnp = self.ws.get("lnp", (L, 2, 2 * d * ops.sas_block_parts(M)), torch.float32)
+        g = dict(dy2=e("dy2", (M, d)), da1=e("da1", (M, d)), dx1=e("dx1", (M, d)), do=e("do", (M, d)))
+        dl = self.ws.get(f"attn_delta{i}", (B * H * T,), torch.float32) if H == 1 else None
+        return dict(g=g, args=(wT[i, 5], wT[i, 4], wT[i, 3], g["dy2"], g["da1"], g["dx1"], g["do"], lnp[i, 0], dl))
+
     def _backward_blocks_fused(self, s, dx, grad, extra_segs=(), tail=None, pos=None):
         """SAS blocks' backward with rs_sas_block_out_bwd / rs_sas_block_in_bwd (rowchain.hip) for the
         row-local chains; then ALL ten weight gradients and the four LayerNorm affine partial sets in
@@ -781,6 +810,9 @@ class SASEngine:
         # per block: the out-side backward's outputs (dy2, da1, dx1, do) and the attention backward's (dq, dkv)
         g = [dict(dy2=e("dy2", (M, d)), da1=e("da1", (M, d)), dx1=e("dx1", (M, d)), do=e("do", (M, d)),
                   dq=e("dq", (M, d)), dkv=e("dkv", (M, 2 * d))) for _ in range(L)]
+        turn = s.get("turnaround")       # the forward's last launch already ran block L-1's output-side backward
+        if turn is not None:
+            g[L - 1].update(turn["g"])
 
         # one head: the out-side backward also forms the attention backward's row term delta = rowsum(dO * O)
         # (the attention kernels then read neither O nor recompute it)
@@ -795,7 +827,8 @@ class SASEngine:
             return (g[i]["dq"], g[i]["dkv"], g[i]["dx1"], s["x"][i], s["mu1"][i], s["r1"][i],
                     self.Wf(f"attention_layernorms.{i}.weight"), wT[i, 0:3].reshape(d, 3 * d))
 
-        ops.sas_block_out_bwd(dx, *out_bwd_args(L - 1))
+        if turn is None:
+            ops.sas_block_out_bwd(dx, *out_bwd_args(L - 1))
         for i in reversed(range(L)):
             pre, fw = f"attention_layers.{i}.", f"forward_layers.{i}."
             dq, dkv, kv = g[i]["dq"], g[i]["dkv"], s["kv"][i]

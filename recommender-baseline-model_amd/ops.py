@@ -610,6 +610,26 @@ def sas_block_in_out_bwd(in_args, dx, part1, out_args):
          ptr(seed_base), ptr(o), ptr(delta), stream())
 
 
+def sas_block_out_head_bwd(out_args, head_args, W2T, W1T, WoT, dy2, da1, dx1, dout, part2, delta=None):
+    """sas_block_out_head(out_args, *head_args) of the last block, then that block's sas_block_out_bwd(dx, ids, h1,
+    x1, mean, rstd, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout, part2, ..., o, delta) on the tile in registers: one
+    launch (rowchain), bitwise the two calls' results except that dx is not written.  head_args' dx: the scratch of
+    the two-launch path, None allowed where sas_block_boundary_fused(M, d)."""
+    (o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
+     seed_base) = out_args
+    E, pos, neg, lnl_w, lnl_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart, part = head_args
+    M, d = o.shape
+    G = sas_block_grid(M)
+    assert part.numel() == 3 * G and lnpart.numel() >= 2 * d * G and count_parts.dtype == torch.int32
+    assert part2.numel() >= 2 * d * G
+    call("rs_sas_block_out_head_bwd", M, d, ptr(o), ptr(Q), ptr(Wo), ptr(bo), ptr(x1), ptr(ln_w), ptr(ln_b), eps,
+         ptr(z), ptr(mean), ptr(rstd), ptr(W1), ptr(b1), ptr(h1), ptr(W2), ptr(b2), ptr(xn), ptr(ids), drop_p, salt1,
+         salt2, ptr(seed_base), ptr(E), ptr(pos), ptr(neg), ptr(lnl_w), ptr(lnl_b), ptr(count_parts),
+         count_parts.numel(), ptr(divisor), ptr(f), ptr(pl), ptr(nl), ptr(dpl), ptr(dnl), ptr(dx), ptr(lnpart),
+         ptr(part), ptr(W2T), ptr(W1T), ptr(WoT), ptr(dy2), ptr(da1), ptr(dx1), ptr(dout), ptr(part2), ptr(delta),
+         stream())
+
+
 # ---- union-of-touched-rows table-gradient exchange (sparse_rows.hip) -------------------------
 def touched_rows_ws_numel(rows):
     return int(_lib.lib().rs_touched_rows_ws_numel(rows))

@@ -209,6 +209,20 @@ def main():
             (qq, dqkv, dx1, x, m1_, r1_, gam, WinT), z, part,
             (ids, h1, x1, m1_, r1_, gam, WT, WT, WT, dy2, da1, dx1, do_, part2, a.drop, 3, 4, sb, None, None)),
             12 * mb)
+        # the forward/backward turnaround: block_out with the head, then block_out_bwd, against both in one kernel
+        Gb = ops.sas_block_grid(M)
+        cntp = torch.full((Gb,), M // Gb, dtype=torch.int32, device=dev)
+        fh, dxh = rn(M, d), rn(M, d)
+        hpl, hnl, hdpl, hdnl = (torch.empty(M, device=dev) for _ in range(4))
+        lnh, hpart, delta = torch.empty(2 * d * Gb, device=dev), torch.empty(3 * Gb, device=dev), torch.empty(M, device=dev)
+        oargs = (oo, Q, W, bias, x1, gam, bet, 1e-8, zz, m1_, r1_, W, bias, h1, W, bias, xn, ids, a.drop, 3, 4, sb)
+        hargs = (table, pos, neg, gam, bet, cntp, None, fh, hpl, hnl, hdpl, hdnl, dxh, lnh, hpart)
+        run("fused block_out_head", lambda: ops.sas_block_out_head(oargs, *hargs), 10 * mb)
+        run("fused block_out_bwd +delta", lambda: ops.sas_block_out_bwd(
+            dxh, ids, h1, x1, m1_, r1_, gam, WT, WT, WT, dy2, da1, dx1, do_, part2, a.drop, 3, 4, sb, o=oo, delta=delta),
+            9 * mb)
+        run("fused block_out_head_bwd", lambda: ops.sas_block_out_head_bwd(
+            oargs, hargs, WT, WT, WT, dy2, da1, dx1, do_, part2, delta), 13 * mb)
         probs = []
         for _ in range(2):
             probs += [(dy2, h1, torch.zeros(d, d, device=dev), torch.zeros(d, device=dev)),
