@@ -371,6 +371,12 @@ int rs_vocab_shard_combine(int N, int64_t R, const float* lse_parts, const float
  * make_plan) of the dK/dV (dkv = 1) or dQ pass; *nsplit = workgroups per sequence.  Returns RS_ERR_UNSUPPORTED
  * where the kernels fall back to one tile per wave (T < 128 or no plan fits). */
 int rs_attn_bwd_plan(int64_t B, int64_t T, int64_t H, int dkv, uint32_t* plan, int* nsplit);
+/* Host-only (no GPU call, no allocation): the code path rs_attn_fwd / rs_attn_bwd take for these arguments, from
+ * the host functions the launchers themselves call.  out[0] = 1: the LDS-resident kernels (attention_lds.hip;
+ * given 16-byte aligned rows), 0: the generic kernels, and then out[1..4] = 0.  out[1] = the forward's workgroups
+ * per sequence-head, out[2] = the backward's, out[3] / out[4] = 1 where the dQ / dK/dV pass runs the work plan
+ * (rs_attn_bwd_plan), 0 where it deals one tile per wave round robin.  mask_kind without RS_ATTN_DELTA_IN. */
+int rs_attn_lds_regime(int dtype, int64_t B, int64_t T, int64_t H, int64_t Dh, int mask_kind, int* out);
 
 /* Kernel stamps (bench.py's in-step timing of the dominant launch; not on the reference's path).
  * While enabled (buf != NULL), rs_attn_bwd (bf16 LDS path), rs_wgrad_grouped and rs_vocab_ce_fwd (its

@@ -57,6 +57,12 @@ __device__ __forceinline__ float masked_score(const AttnArgs& a, int64_t b, int6
   return a.ids[b * a.T + key] == 0 ? -1e9f : s;                     // key padding (single.py:28)
 }
 
+// the score of this key was replaced by the -1e9 fill: masked_fill passes no gradient, so dS = 0 there.  (P of a
+// filled key is 0 beside any live key, but 1 in a row whose keys are all padding.)
+__device__ __forceinline__ bool score_filled(const AttnArgs& a, int64_t b, int64_t key) {
+  return a.mask_kind == 1 && key < a.T && a.ids[b * a.T + key] == 0;
+}
+
 // 8 elements of row `row`, columns [col, col+8) (zero past rlim rows / dh columns)
 // exp / log of the generic kernels: the fp32 (parity) instantiations use the accurate libm forms, as the reference's
 // torch softmax does (the fast forms' argument rounding -- exp2(x * log2 e) -- adds noise that a 1000-step training
@@ -291,7 +297,8 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(AttnArgs a) {
         float p = (x == NEG_INF || qrow >= a.T) ? 0.f : aexp<T>(x - lse[r]);
         float dpe = dp[r];
         if (a.drop_p > 0.f) dpe *= drop_mul(a.drop_p, seed, (uint64_t)((bh * a.T + qrow) * tp + key));
-        dSs[(4 * g + r) * SLD + half * 16 + cl] = from_f<T>(p * (dpe - dl[r]) * a.scale);
+        const float ds = score_filled(a, b, key) ? 0.f : p * (dpe - dl[r]) * a.scale;
+        dSs[(4 * g + r) * SLD + half * 16 + cl] = from_f<T>(ds);
       }
     }
     stage_transposed<T, DHP>(Kt, SLD, K, a.ldk, (int64_t)kc * 32, a.T, lane, a.Dh, a.vec);
@@ -371,7 +378,8 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_kernel(AttnArgs a) {
         float p = (x == NEG_INF || qrow >= a.T || key >= a.T) ? 0.f : aexp<T>(x - lq);
         float dm = a.drop_p > 0.f ? drop_mul(a.drop_p, seed, (uint64_t)((bh * a.T + qrow) * tp + key)) : 1.f;
         Pt[(4 * g + r) * SLD + half * 16 + cl] = from_f<T>(p * dm);
-        dSt[(4 * g + r) * SLD + half * 16 + cl] = from_f<T>(p * (dpt[r] * dm - dq) * a.scale);
+        const float ds = score_filled(a, b, key) ? 0.f : p * (dpt[r] * dm - dq) * a.scale;
+        dSt[(4 * g + r) * SLD + half * 16 + cl] = from_f<T>(ds);
       }
     }
     stage_transposed<T, DHP>(Qt, SLD, Q, a.ldq, qc, a.T, lane, a.Dh, a.vec);
@@ -509,7 +517,20 @@ __global__ __launch_bounds__(256) void row_delta_v8_kernel(int64_t M, int64_t T,
   }
 }
 
+void attn_lds_regime(int64_t B, int64_t T, int64_t H, int64_t Dh, int mask_kind, int* out);
+
 extern "C" {
+
+int rs_attn_lds_regime(int dtype, int64_t B, int64_t T, int64_t H, int64_t Dh, int mask_kind, int* out) {
+  if (!out || (mask_kind != 0 && mask_kind != 1)) return RS_ERR_ARG;
+  int c = check(B, T, H, Dh);
+  if (c) return c;
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (!use_lds_path(dtype, B * H, T, Dh)) return RS_OK;
+  out[0] = 1;
+  attn_lds_regime(B, T, H, Dh, mask_kind, out + 1);
+  return RS_OK;
+}
 
 int rs_attn_row_delta(int dtype, int64_t B, int64_t T, int64_t H, int64_t Dh, const void* dout, int64_t lddo,
                       const void* o, int64_t ldo, float* delta, void* stream) {

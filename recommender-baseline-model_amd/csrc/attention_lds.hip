@@ -621,7 +621,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnLdsArgs& a, int64_t l
     }
     float* sl = slots + slot * (DT * 4 * 64);
     if (role == 1) {
-      // upper key half: partial dQ -> LDS slot, then release it to the lower half's wave
+      // lower key half (the writer): partial dQ -> LDS slot, then release it to the upper half's wave
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -875,7 +875,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnLdsArgs& a, int64_t 
     }
     bf16* sl = slots + slot * (2 * DT * 4 * 64);
     if (role == 1) {
-      // upper query half: partial (dK, dV) -> LDS slot (bf16), then release it to the lower half's wave
+      // lower query half (the writer): partial (dK, dV) -> LDS slot (bf16), then release it to the upper half's wave
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -967,10 +967,12 @@ bool attn_lds_supported(int64_t T, int64_t Dh) {
   return need <= 160 * 1024;
 }
 
+// the forward's workgroups per sequence-head (the launcher and rs_attn_lds_regime)
+static int fwd_split(const AttnLdsArgs& a) { return pick_split(a.B * a.H, (int)cdiv(a.T, 16)); }
+
 template <int DH>
 static hipError_t fwd_t(AttnLdsArgs& a, hipStream_t s) {
-  const int nq = (int)cdiv(a.T, 16);
-  a.nsplit = pick_split(a.B * a.H, nq);
+  a.nsplit = fwd_split(a);
   const size_t lds = fwd_lds_bytes<DH>((int)a.T);
   hipLaunchKernelGGL((attn_fwd_lds_kernel<DH>), dim3((unsigned)a.nsplit, (unsigned)(a.B * a.H)), dim3(NT), lds, s,
                      a);
@@ -1060,22 +1062,46 @@ extern "C" int rs_attn_bwd_plan(int64_t B, int64_t T, int64_t H, int dkv, uint32
   return ok ? 0 : RS_ERR_UNSUPPORTED;
 }
 
+// the backward's regime: a.nsplit, the two passes' arguments with their plans (use_plan 0: one tile per wave
+// round robin) and the launch's LDS bytes (the launcher and rs_attn_lds_regime)
 template <int DH>
-static hipError_t bwd_t(AttnLdsArgs& a, hipStream_t s) {
+static size_t bwd_setup(AttnLdsArgs& a, AttnLdsArgs& aq, AttnLdsArgs& akv) {
   const int nq = (int)cdiv(a.T, 16);
   a.nsplit = pick_split_bwd(a.B * a.H, nq);
   constexpr int DT = DH / 16;
   const size_t lds_q = fwd_lds_bytes<DH>((int)a.T), lds_kv = dkv_lds_bytes<DH>((int)a.T);
   const size_t ext_q = (size_t)DQ_SLOTS * DT * 4 * 64 * 4 + 16, ext_kv = (size_t)DKV_SLOTS * 2 * DT * 4 * 64 * 2 + 16;
-  AttnLdsArgs aq = a, akv = a;
+  aq = a;
+  akv = a;
   // only long causal sequences: at T = 50 (4 tiles) the split halves cost more than the imbalance they remove
   const bool want = a.mask_kind == 0 && nq >= 8;
   aq.use_plan = want && lds_q + ext_q <= 160 * 1024 && make_plan(aq, nq, false, DQ_SLOTS);
   akv.use_plan = want && lds_kv + ext_kv <= 160 * 1024 && make_plan(akv, nq, true, DKV_SLOTS);
   const size_t bq = lds_q + (aq.use_plan ? ext_q : 0), bkv = lds_kv + (akv.use_plan ? ext_kv : 0);
-  hipLaunchKernelGGL((attn_bwd_lds_kernel<DH>), dim3((unsigned)(2 * a.nsplit * a.B * a.H)), dim3(NT),
-                     std::max(bq, bkv), s, aq, akv);
+  return std::max(bq, bkv);
+}
+
+template <int DH>
+static hipError_t bwd_t(AttnLdsArgs& a, hipStream_t s) {
+  AttnLdsArgs aq, akv;
+  const size_t lds = bwd_setup<DH>(a, aq, akv);
+  hipLaunchKernelGGL((attn_bwd_lds_kernel<DH>), dim3((unsigned)(2 * a.nsplit * a.B * a.H)), dim3(NT), lds, s, aq,
+                     akv);
   return hipGetLastError();
+}
+
+// host-only: out[0..3] = forward nsplit, backward nsplit, dQ plan used, dK/dV plan used -- from the launchers' own
+// helpers (rs_attn_lds_regime; the plans themselves: rs_attn_bwd_plan)
+void attn_lds_regime(int64_t B, int64_t T, int64_t H, int64_t Dh, int mask_kind, int* out) {
+  AttnLdsArgs a = {}, aq, akv;
+  a.B = B; a.T = T; a.H = H; a.mask_kind = mask_kind;
+  out[0] = fwd_split(a);
+  if (Dh == 128) bwd_setup<128>(a, aq, akv);
+  else if (Dh == 64) bwd_setup<64>(a, aq, akv);
+  else bwd_setup<32>(a, aq, akv);
+  out[1] = a.nsplit;
+  out[2] = aq.use_plan;
+  out[3] = akv.use_plan;
 }
 
 template <int DH>
