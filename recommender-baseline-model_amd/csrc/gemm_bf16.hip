@@ -8,6 +8,9 @@ namespace gbf {
 int epi_class(const GemmArgs& a) {
   const rs_epilogue& e = a.epi;
   if (!a.vec_ok || e.alpha != 1.0f) return EC_GENERIC;
+  // the typed classes draw the masks of element pairs {2j, 2j + 1} from one hash (drop_mul2) starting at the even
+  // index m * drop_ld + n, n a multiple of 8: an odd drop_ld would pair the elements of odd rows wrongly
+  if ((e.drop_p > 0.f || e.post_drop_p > 0.f) && (e.drop_ld & 1)) return EC_GENERIC;
   int ec = 0;
   if (e.bias) ec |= EB;
   if (e.drop_p > 0.f) ec |= ED;

@@ -345,6 +345,27 @@ __global__ __launch_bounds__(256) void ln_bwd_v_kernel(const T* __restrict__ X, 
   }
 }
 
+// The dropout site(s) of rs_layernorm_bwd_drop for shapes off the vectorised path: dX read at its pitch lddx, out1 /
+// out2 dense [M][d], hash index row * d + column, the roundings of the fused form above (out1 = round(dX m1),
+// out2 = round(out1 m2)).  rs_dropout2 / rs_dropout_rowmask do not serve here: they write at the INPUT's pitch (out1
+// is dense by contract) and rs_dropout2 takes multiples of 8 columns only (d = 50).
+template <typename T>
+__global__ __launch_bounds__(256) void ln_drop_sites_kernel(const T* __restrict__ dX, int64_t lddx, int64_t M, int d,
+                                                            float p, uint64_t salt1, uint64_t salt2,
+                                                            const uint64_t* seed_base, T* __restrict__ out1,
+                                                            T* __restrict__ out2) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= M * d) return;
+  const int64_t m = i / d, c = i - m * d;
+  float v = to_f(dX[m * lddx + c]);
+  if (p > 0.f) v = to_f(from_f<T>(v * drop_mul(p, eff_seed(salt1, seed_base), (uint64_t)i)));
+  out1[i] = from_f<T>(v);
+  if (out2) {
+    if (p > 0.f) v *= drop_mul(p, eff_seed(salt2, seed_base), (uint64_t)i);
+    out2[i] = from_f<T>(v);
+  }
+}
+
 template <typename T>
 static hipError_t ln_fwd_t(const void* X, int64_t ldx, int64_t M, int d, const float* gamma, const float* beta,
                            float eps, int variant, void* Y, int64_t ldy, float* mean, float* rinv, hipStream_t s) {
@@ -500,8 +521,14 @@ int rs_layernorm_bwd_drop(int dtype, int variant, const void* X, int64_t ldx, co
   if (int r = rs_layernorm_bwd(dtype, variant, X, ldx, dY, lddy, M, d, gamma, mean, rinv, eps, dX, lddx,
                                accumulate_dx, dgamma, dbeta, ws, stream))
     return r;
-  return out2 ? rs_dropout2(dtype, dX, M, d, lddx, drop_p, salt1, salt2, seed_base, d, out1, out2, stream)
-              : rs_dropout_rowmask(dtype, dX, M, d, lddx, drop_p, salt1, seed_base, d, nullptr, out1, nullptr, stream);
+  const dim3 grid((unsigned)cdiv(M * d, 256));
+  if (dtype == RS_DTYPE_BF16)
+    hipLaunchKernelGGL(ln_drop_sites_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dX, lddx, M, (int)d, drop_p,
+                       salt1, salt2, seed_base, (__bf16*)out1, (__bf16*)out2);
+  else
+    hipLaunchKernelGGL(ln_drop_sites_kernel<float>, grid, dim3(256), 0, s, (const float*)dX, lddx, M, (int)d, drop_p,
+                       salt1, salt2, seed_base, (float*)out1, (float*)out2);
+  return (int)hipGetLastError();
 }
 
 int rs_layernorm_bwd(int dtype, int variant, const void* X, int64_t ldx, const void* dY, int64_t lddy,
