@@ -745,6 +745,48 @@ int rs_sas_ce_rows_bwd(int dtype, int64_t M, int64_t d, const float* slab, int s
                        const int32_t* rank, const void* x, int64_t ldx, const float* gamma, const float* mean,
                        const float* rstd, void* dx, int64_t lddx, float* part, void* stream);
 
+/* ---- SASRec sampled-softmax head over batch-shared candidates (sas_sce.hip) ----
+ * The objective, on the compact valid rows rs_sas_ce_rows_fwd leaves (or on all rows with count NULL: lab 0 = no row):
+ *   f_r   = last_layernorm(log2feats(seq))[r]          for every position r with pos_r != 0 ("valid")
+ *   z_r0  = <f_r, E[pos_r]>                            E = item_emb.weight (tied), fp32 accumulate
+ *   z_rj  = <f_r, E[cand_j]>,  j = 1..K                cand: int64 [K], ids in [0, V]
+ *   live(r, j) = cand_j != 0 and cand_j != pos_r       id 0 = an ignored slot; accidental hits masked
+ *   loss  = (1 / max(n, 1)) * sum_valid r [ log( exp(z_r0) + sum_{live j} exp(z_rj) ) - z_r0 ],   n = #valid
+ * Duplicate ids in cand are separate classes (each counts); no logQ correction; a row with no live candidate has loss
+ * 0 and gradient 0; an id outside [0, V] counts as 0.  With p_rj = softmax over {0} + live and s = *dloss / *divisor:
+ *   dh[r]   = s ((p_r0 - 1) E[pos_r] + sum_live p_rj E[cand_j])     fp32 slabs [splits][cap][d], splits =
+ *                                                                   rs_sas_sce_dh_splits(cap, K, d) (host only): one
+ *                                                                   per split of the candidates, to be summed in
+ *                                                                   split order (rs_sas_ce_rows_bwd(splits))
+ *   coef[r] = s (p_r0 - 1),   pg[r] = coef[r] hl[r]                 fp32 [cap], [cap][d]: the table's gradient at pos_r
+ *   dEc[j]  = s sum_r p_rj hl[r]                                    fp32 [K][d]: the table's gradient at cand_j, the
+ *                                                                   rows summed in a fixed order (row splits in fp32
+ *                                                                   slabs reduced in split order; no atomics)
+ *   keys    (nullable) int64 [cap + K]: lab of the rows < *count (0 past it), then cand -- the inverted index's keys
+ *           over the rows of {pg, dEc} (rs_item_index_build, rs_item_grad_f32: key 0 gets nothing)
+ * hl: [cap][d] rows of stride ldh, lab [cap], count: device int32 (NULL: cap), E: [V1][d] in hl's dtype, divisor:
+ * device float (max(n, 1)), dloss: device float or NULL (1).  rs_sas_sce_fwd writes lse and z_r0 per row into ws and
+ * out = {loss sum, n, sum / *divisor}; rs_sas_sce_bwd reads them there.  Rows at or past *count are left untouched in
+ * every per-row output.  ws: rs_sas_sce_ws_bytes(cap, K, d) bytes (host only; no argument for V: nothing here is
+ * sized by the catalogue), 16-byte aligned.  dtype fp32 (any d <= 1024) or bf16 (d % 8 == 0, d <= 1024; d <= 128 runs
+ * the MFMA sweep, wider rows a plain kernel with the same outputs), 1 <= K <=
+ * rs_sas_sce_max_k() (65536); anything else: RS_ERR_UNSUPPORTED, nothing launched.  No allocation, no sync,
+ * graph-capturable; the logits are never stored.
+ * rs_uniform_items: out[j] = 1 + floor(u_j * item_num), u_j uniform from splitmix64 of (salt ^ f(*seed_base), j):
+ * K draws with replacement over [1, item_num].  It advances nothing (the sampler's own kernel advances seed_base). */
+int64_t rs_sas_sce_max_k(void);
+int64_t rs_sas_sce_ws_bytes(int64_t cap, int64_t K, int64_t d);
+int64_t rs_sas_sce_dh_splits(int64_t cap, int64_t K, int64_t d);
+int rs_sas_sce_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                   const int32_t* count, const void* E, int64_t V1, const int64_t* cand, int64_t K,
+                   const float* divisor, void* ws, float* out, void* stream);
+int rs_sas_sce_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                   const int32_t* count, const void* E, int64_t V1, const int64_t* cand, int64_t K,
+                   const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
+                   int64_t* keys, void* stream);
+int rs_uniform_items(const uint64_t* seed_base, uint64_t salt, int64_t item_num, int64_t K, int64_t* out,
+                     void* stream);
+
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);
 

@@ -35,9 +35,13 @@ def _flatten(histories, device):
 class DeviceWarpSampler:
     n_outputs = 3
 
-    def __init__(self, user_train, item_num, batch_size, max_len, device="cuda", num_workers=None, seed=None):
+    def __init__(self, user_train, item_num, batch_size, max_len, device="cuda", num_workers=None, seed=None,
+                 shared_negs=None):
         """user_train: list (per user) of item-id lists, as ``data_partition`` builds it.
-        num_workers is accepted for signature compatibility and ignored."""
+        num_workers is accepted for signature compatibility and ignored.
+        shared_negs=K: batches are (seq, pos, cand) with cand int64 (K,) drawn uniformly with replacement from
+        [1, item_num] on the device (rs_uniform_items: the same advanced step seed, its own salt) -- the candidates
+        of the sampled-softmax loss, shared by the whole batch; the per-position neg goes to a private buffer."""
         if max_len > 512:
             raise ValueError("max_len must be <= 512")
         self.device = torch.device(device)
@@ -50,15 +54,34 @@ class DeviceWarpSampler:
         self.salt = int(torch.randint(0, 2 ** 62, (1,), generator=g).item())
         self.seed_base = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.cnt = 0
+        self.shared_negs = None if shared_negs is None else int(shared_negs)
+        if self.shared_negs is not None:
+            if self.shared_negs < 1:
+                raise ValueError("shared_negs must be a positive number of candidates")
+            self.cand_salt = int(torch.randint(0, 2 ** 62, (1,), generator=g).item())
+            self._neg = torch.empty((self.batch_size, self.max_len), dtype=torch.int64, device=self.device)
 
     def sample_into(self, seq, pos, neg, draws=None):
         """Write the next batch into existing (batch_size, max_len) int64 device tensors (draws: see
-        ops.sas_sample)."""
+        ops.sas_sample).  With shared_negs=K the third tensor is cand, int64 (K,)."""
+        if self.shared_negs is not None:
+            cand = neg
+            if cand.shape != (self.shared_negs,) or cand.dtype != torch.int64 or not cand.is_contiguous():
+                raise ValueError(f"cand must be a contiguous int64 tensor of shape ({self.shared_negs},)")
+            ops.sas_sample(self.offsets, self.items, self.n_users, self.item_num, self.seed_base, self.salt, seq, pos,
+                           self._neg, draws)
+            ops.uniform_items(self.seed_base, self.cand_salt, self.item_num, cand)   # the seed the launch above advanced
+            return
         ops.sas_sample(self.offsets, self.items, self.n_users, self.item_num, self.seed_base, self.salt, seq, pos, neg,
                        draws)
 
     def sample(self):
         shape = (self.batch_size, self.max_len)
+        if self.shared_negs is not None:
+            seq, pos = (torch.empty(shape, dtype=torch.int64, device=self.device) for _ in range(2))
+            cand = torch.empty(self.shared_negs, dtype=torch.int64, device=self.device)
+            self.sample_into(seq, pos, cand)
+            return seq, pos, cand
         seq, pos, neg = (torch.empty(shape, dtype=torch.int64, device=self.device) for _ in range(3))
         self.sample_into(seq, pos, neg)
         return seq, pos, neg

@@ -26,6 +26,9 @@ Adam (rs_adam_prepare_step_loss).
 loss="ce" (ce_forward / ce_backward): the blocks without the in-block head, then on the rows with pos != 0 only
 rs_sas_ce_rows_fwd -> rs_vocab_head_fwd / _bwd against the whole item table (tied) -> rs_linear_wgrad (dE) -> rs_gemm
 (dh) -> rs_sas_ce_rows_bwd, and the blocks' backward with the item index over the input ids alone.
+loss="sampled_ce" (sce_forward / sce_backward): the same, with the vocabulary kernels replaced by the sampled-softmax
+head over K candidates shared by the batch (sas_sce.hip): rs_sas_sce_fwd -> rs_sas_sce_bwd (dh, the positives'
+coefficients, dEc) -> rs_item_index_build + rs_item_grad_f32 over the cap + K head keys -> rs_sas_ce_rows_bwd.
 fp32 parity mode and other widths run the generic unfused kernels: rs_embed_fwd, rs_layernorm_fwd/bwd (variant 0,
 eps 1e-8), rs_gemm (MFMA, fused bias / ReLU / dropout / residual / row-mask epilogues), rs_attn_fwd/bwd,
 rs_sampled_logits_fwd/bwd, rs_bce_*, split-K weight gradients.
@@ -41,7 +44,8 @@ from ...engine_util import Workspace, as_ids, capture_event, compute_dtype, requ
 from ...flat import FlatParams
 
 LN_EPS = 1e-8
-SAS_LOSSES = ("bce", "ce")
+SAS_LOSSES = ("bce", "ce", "sampled_ce")
+SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
 
 
 class PointWiseFeedForward(nn.Module):
@@ -67,10 +71,15 @@ class SAS(nn.Module):
         # the trainer's l2 regulariser weight (BS/trainers/sas.py:14,51-52), applied by FusedTrainStep
         self.l2_emb = float(getattr(args, "l2_emb", 0.0) or 0.0)
         # the training objective FusedTrainStep takes by default: "bce" (the reference's one sampled negative per
-        # position) or "ce" (softmax cross-entropy over the whole catalogue, the item table tied as output layer)
+        # position), "ce" (softmax cross-entropy over the whole catalogue, the item table tied as output layer) or
+        # "sampled_ce" (the same softmax over the positive and sas_shared_negs candidates shared by the batch)
         self.sas_loss = str(getattr(args, "sas_loss", None) or "bce")
         if self.sas_loss not in SAS_LOSSES:
             raise ValueError(f"sas_loss must be one of {SAS_LOSSES}, got {self.sas_loss!r}")
+        # sas_loss="sampled_ce": the number of candidates (negatives shared by the whole batch) per step
+        self.sas_shared_negs = int(getattr(args, "sas_shared_negs", 0) or 0)
+        if self.sas_loss == "sampled_ce" and self.sas_shared_negs < 1:
+            raise ValueError("sas_loss='sampled_ce' needs args.sas_shared_negs = K > 0 (the shared candidates)")
         self.cdtype = compute_dtype(args)
         d = self.hidden
         if d % self.heads:
@@ -135,6 +144,26 @@ class SAS(nn.Module):
         params = [p for _, p in self.named_parameters()]
         return _SASCEFunction.apply(eng, ids, pos, self.training, *params)
 
+    def sampled_ce_loss(self, log_seqs, pos_seqs, cand):
+        """Scalar loss of the sampled softmax over batch-shared candidates (differentiable; available whatever
+        sas_loss says).  cand: int64 (K,), ids in [0, V], shared by every position:
+
+            f_r   = last_layernorm(log2feats(seq))[r]          for every position r with pos_r != 0 ("valid")
+            z_r0  = <f_r, E[pos_r]>                            E = item_emb.weight (tied)
+            z_rj  = <f_r, E[cand_j]>,  j = 1..K
+            live(r, j) = cand_j != 0 and cand_j != pos_r       id 0 = an ignored slot; accidental hits masked
+            loss  = (1 / max(n, 1)) * sum_valid r [ log(exp(z_r0) + sum_{live j} exp(z_rj)) - z_r0 ],   n = #valid
+
+        Duplicate candidates count separately; there is no logQ correction; with cand = arange(1, V + 1) it is
+        ce_loss up to the padding class 0 (logit exactly 0), which ce_loss counts and no candidate list can name.
+        A row with no live candidate, and a batch with no valid row, give loss 0 and zero gradients; row 0 of the
+        item table gets no gradient.  Call backward() before the next loss call."""
+        eng = self.engine()
+        dev = self._flat.device
+        ids, pos, cand = as_ids(log_seqs, dev), as_ids(pos_seqs, dev), as_ids(cand, dev)
+        params = [p for _, p in self.named_parameters()]
+        return _SASSCEFunction.apply(eng, ids, pos, cand, self.training, *params)
+
     def log2feats(self, log_seqs):
         eng = self.engine()
         ids = as_ids(log_seqs, self._flat.device)
@@ -198,6 +227,25 @@ class _SASCEFunction(torch.autograd.Function):
         ctx.saved = None
         grads = [eng.flat.view(n, grad) for n in eng.flat.names]
         return (None, None, None, None, *grads)
+
+
+class _SASSCEFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, ids, pos, cand, training, *params):
+        engine.sync_compute_weights()
+        out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
+        ctx.saved = engine.sce_forward(ids, pos, cand, training, out)
+        ctx.engine = engine
+        return out[2].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        eng = ctx.engine
+        grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
+        eng.sce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
+        ctx.saved = None
+        grads = [eng.flat.view(n, grad) for n in eng.flat.names]
+        return (None, None, None, None, None, *grads)
 
 
 class SASEngine:
@@ -597,20 +645,11 @@ class SASEngine:
         RS_SAS_CE_ROWS=0 selects the composed launches they replace (A/B timing, tools/sas_ce_bench.py)."""
         return ops.sas_ce_rows_ok(self.d, self.dt) and os.environ.get("RS_SAS_CE_ROWS", "1") != "0"
 
-    def ce_forward(self, ids, pos, training, loss_out, max_labelled=None, clone_seed=True):
-        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and CrossEntropy(ignore_index=0)
-        of the logits against the whole item table (tied; class 0 is the zero padding row), never materialised in
-        bf16.  loss_out (fp32 [>= 3], device) = {loss sum, valid count, mean}; a batch without a valid row gives
-        mean 0.  max_labelled: upper bound on the valid rows (sizes the compact buffers; default B*T; rows past it
-        are dropped as rs_compact_rows does).  Returns the saved state for ce_backward.  Buffers are the engine's
-        workspace; nothing here allocates per step or reads the host."""
+    def _valid_rows_forward(self, s, pos, max_labelled):
+        """The last LayerNorm on the rows with pos != 0, compacted (the front half of both softmax heads): hl [cap][d],
+        lab [cap], the device row count and the mean's divisor max(count, 1), in the engine's ce_* buffers."""
         d, dt = self.d, self.dt
-        if dt == torch.bfloat16 and d % 8:
-            raise ValueError(f"the bf16 cross-entropy head needs hidden units divisible by 8 (got {d}); "
-                             "use fp32 mode (rs_dtype='fp32') at this width")
-        B, T = ids.shape
-        M = B * T
-        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
+        M = s["B"] * s["T"]
         f32 = torch.float32
         g = self.ws.get
         # fp32 rows that are no multiple of 16 bytes (the reference's d = 50): the compaction kernels do not take
@@ -625,7 +664,6 @@ class SASEngine:
         if "ce_hl" not in self.ws.bufs or tuple(self.ws.bufs["ce_hl"].shape) != (cap, d):
             g("ce_hl", (cap, d), dt).zero_()      # rows past the live count are never written: start them finite
         hl, lab, div = g("ce_hl", (cap, d), dt), g("ce_lab", (cap,), torch.int64), g("ce_div", (1,), f32)
-        E = self.W("item_emb.weight")
         gl, bl = self.Wf("last_layernorm.weight"), self.Wf("last_layernorm.bias")
         rows_fused = self.ce_rows_fused
         if dense:
@@ -641,6 +679,26 @@ class SASEngine:
             ops.compact_rows(labels, cap, idx, rank, cnt)
             ops.gather_rows(f, idx, cnt, cap, hl, labels, lab)
             div.copy_(cnt).clamp_(min=1)          # the mean's divisor: max(count, 1)
+        return dict(cap=cap, V1=V1, V1p=V1p, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, mu=mu, rs=rs,
+                    rows_fused=rows_fused, dense=dense)
+
+    def ce_forward(self, ids, pos, training, loss_out, max_labelled=None, clone_seed=True):
+        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and CrossEntropy(ignore_index=0)
+        of the logits against the whole item table (tied; class 0 is the zero padding row), never materialised in
+        bf16.  loss_out (fp32 [>= 3], device) = {loss sum, valid count, mean}; a batch without a valid row gives
+        mean 0.  max_labelled: upper bound on the valid rows (sizes the compact buffers; default B*T; rows past it
+        are dropped as rs_compact_rows does).  Returns the saved state for ce_backward.  Buffers are the engine's
+        workspace; nothing here allocates per step or reads the host."""
+        d, dt = self.d, self.dt
+        if dt == torch.bfloat16 and d % 8:
+            raise ValueError(f"the bf16 cross-entropy head needs hidden units divisible by 8 (got {d}); "
+                             "use fp32 mode (rs_dtype='fp32') at this width")
+        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
+        f32 = torch.float32
+        g = self.ws.get
+        c = self._valid_rows_forward(s, pos, max_labelled)
+        cap, V1, V1p, cnt, hl, lab, div = (c[k] for k in ("cap", "V1", "V1p", "cnt", "hl", "lab", "div"))
+        E = self.W("item_emb.weight")
         if dt == torch.bfloat16:
             wce = g("ce_vce", (ops.vocab_ce_ws_numel(cap, V1),), f32)
             fwd = ops.vocab_head_fwd if ops.vocab_head_supported(d) else ops.vocab_ce_fwd
@@ -651,8 +709,8 @@ class SASEngine:
             ops.linear_fwd(hl, E, dl, rows_dev=cnt)
             wce = g("ce_wce", (3 * cap,), f32)
             ops.ce_fwd(dl, lab, wce, loss_out, div, rows_dev=cnt)
-        s.update(ce=dict(cap=cap, V1=V1, V1p=V1p, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, mu=mu, rs=rs, wce=wce,
-                         dl=dl, rows_fused=rows_fused, dense=dense))
+        c.update(wce=wce, dl=dl)
+        s.update(ce=c)
         return s
 
     def ce_backward(self, s, grad, dloss=None):
@@ -663,9 +721,7 @@ class SASEngine:
         input ids (rs_item_grad, one writer per row), which the fused path runs on the side stream only after the
         blocks' backward: one writer at a time, fixed order, no float atomics."""
         c = s["ce"]
-        B, T, p, ids = s["B"], s["T"], s["p"], s["ids"]
-        M, d = B * T, self.d
-        sb, dt = s["sb"], self.dt
+        d, dt = self.d, self.dt
         f32 = torch.float32
         g = self.ws.get
         G = lambda n: self.flat.view(n, grad)  # noqa: E731
@@ -686,6 +742,21 @@ class SASEngine:
         sk = int(max(1, min(64, -(-V1 // 2048))))
         slab_d = g("ce_slab_dh", (sk * cap * d,), f32)
         ops.gemm(dl, E, slab_d, cap, d, V1, False, True, ops.epilogue(rows_dev=cnt), split_k=sk, slab=slab_d)
+        self._valid_rows_backward(s, grad, slab_d, sk)
+
+    def _valid_rows_backward(self, s, grad, slab_d, sk, after_rows=None):
+        """From dh on the compact rows (fp32 slab_d [sk][cap][d], summed in split order): the last LayerNorm's
+        backward scattered to all rows, the blocks' backward and the lookup part of the item table's gradient (the
+        back half of both softmax heads).  after_rows(): called once the LayerNorm backward has been issued."""
+        c = s["ce"]
+        B, T, p, ids = s["B"], s["T"], s["p"], s["ids"]
+        M, d = B * T, self.d
+        sb, dt = s["sb"], self.dt
+        f32 = torch.float32
+        g = self.ws.get
+        G = lambda n: self.flat.view(n, grad)  # noqa: E731
+        cap = c["cap"]
+        GE = G("item_emb.weight")
         gl = self.Wf("last_layernorm.weight")
         fused = ops.sas_block_fused_ok(d, dt)
         dx = g("ce_dx", (M, d), dt)
@@ -706,6 +777,8 @@ class SASEngine:
             ops.layernorm_bwd(s["xL"], df, gl, c["mu"], c["rs"], LN_EPS, dx, G("last_layernorm.weight"),
                               G("last_layernorm.bias"), wln, 0)
             segs = []
+        if after_rows is not None:
+            after_rows()
         if not fused:
             by_index = dt == torch.float32 or d in (64, 128, 256)
             self._backward_blocks_unfused(s, dx, grad, by_index, [ids], None, None, None)
@@ -719,6 +792,77 @@ class SASEngine:
         self._backward_blocks_fused(s, dx, grad, segs, tail=item_grads,
                                     pos=lambda dx: (ids, T, dx, p, self.salt["emb"], sb, G("pos_emb.weight")))
         torch.cuda.current_stream().wait_event(self._tail_join)
+
+    # ---- sampled softmax over batch-shared candidates (sas_sce.hip) ----------------------------
+    def _sce_cand(self, cand):
+        cand = cand.reshape(-1).contiguous()
+        K, kmax = cand.numel(), ops.sas_sce_max_k()
+        if K < 1 or K > kmax:
+            raise ValueError(f"the sampled-softmax head takes 1 .. {kmax} shared candidates, got {K}")
+        return cand
+
+    def sce_forward(self, ids, pos, cand, training, loss_out, max_labelled=None, clone_seed=True):
+        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and the softmax cross-entropy of
+        the positive against the K candidates `cand` (int64 [K], shared by every row; id 0 and a row's own positive
+        are masked; SAS.sampled_ce_loss has the definition).  loss_out = {loss sum, valid count, mean}.  Returns the
+        saved state for sce_backward.  The sce_* buffers are sized by (cap, K, d) alone; nothing here allocates per
+        step or reads the host."""
+        d, dt = self.d, self.dt
+        if dt == torch.bfloat16 and d % 8:
+            raise ValueError(f"the bf16 sampled-softmax head needs hidden units divisible by 8 (got {d}); "
+                             "use fp32 mode (rs_dtype='fp32') at this width")
+        if not ops.sas_sce_ok(d, dt):
+            raise ValueError(f"the sampled-softmax head covers hidden units up to 1024 (got {d})")
+        cand = self._sce_cand(cand)
+        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
+        c = self._valid_rows_forward(s, pos, max_labelled)
+        ws = self.ws.get("sce_ws", (ops.sas_sce_ws_numel(c["cap"], cand.numel(), d),), torch.float32)
+        ops.sas_sce_fwd(c["hl"], c["lab"], c["cnt"], c["cap"], self.W("item_emb.weight"), cand, c["div"], ws, loss_out)
+        c.update(cand=cand, sce_ws=ws)
+        s.update(ce=c)
+        return s
+
+    def sce_backward(self, s, grad, dloss=None):
+        """Accumulates every parameter gradient of sce_forward's loss (times *dloss, a device scalar, if given) into
+        the flat fp32 buffer ``grad``.  The head's part of the item table's gradient -- coef_r f_r at row pos_r and
+        dEc[j] at row cand_j -- goes through an inverted index of its own (rs_item_index_build over the cap + K keys,
+        rs_item_grad_f32: one writer per table row, duplicates summed in sorted-entry order), on the side stream
+        beside the blocks' backward (fused path; else on the main stream); the lookup part follows on that same
+        stream after the blocks' backward, as in ce_backward: one writer at a time, fixed order, no float atomics."""
+        c = s["ce"]
+        d = self.d
+        f32 = torch.float32
+        g = self.ws.get
+        cap, cnt, hl, lab, cand = c["cap"], c["cnt"], c["hl"], c["lab"], c["cand"]
+        K = cand.numel()
+        GE = self.flat.view("item_emb.weight", grad)
+        sk = ops.sas_sce_dh_splits(cap, K, d)          # one fp32 slab per split of the candidates
+        dh, coef = g("sce_dh", (sk, cap, d), f32), g("sce_coef", (cap,), f32)
+        src, keys = g("sce_src", (cap + K, d), f32), g("sce_keys", (cap + K,), torch.int64)
+        ops.sas_sce_bwd(hl, lab, cnt, cap, self.W("item_emb.weight"), cand, c["div"], dloss, c["sce_ws"], dh, coef,
+                        src[:cap], src[cap:], keys)
+        # the index's key range: at least past the counting sort's table limit, so that the radix path is taken and
+        # the workspace is sized by the entry count alone (the counting sort's histograms are sized by the table)
+        rows = max(GE.shape[0], SCE_INDEX_ROWS)
+        iws = g("sce_itemidx", (ops.item_index_ws_bytes(1, cap + K, rows, d),), torch.uint8)
+
+        def head_table_grad():
+            ops.item_index_build([keys], rows, d, iws)
+            ops.item_grad(iws, 1, cap + K, src, 1.0, 0.0, 0, s["sb"], None, None, None, GE, table_rows=rows)
+        after_rows = head_table_grad
+        if ops.sas_block_fused_ok(d, self.dt) and "side" in s:
+            # the fused path: these launches depend on the head alone, so they run on the side stream beside the
+            # LayerNorm and blocks' backward; the lookup part is issued on the same stream later and the step joins
+            # it (_tail_join), so the table still has one writer at a time, in a fixed order.  Issued after the main
+            # stream's next launch: the captured graph keeps a node's first child on its queue
+            ev = capture_event()
+            ev.record(torch.cuda.current_stream())
+
+            def after_rows():
+                self._side.wait_event(ev)
+                with torch.cuda.stream(self._side):
+                    head_table_grad()
+        self._valid_rows_backward(s, grad, dh, sk, after_rows=after_rows)
 
     def enable_row_marks(self, min_rows=0):
         """Stamp the rows the inverted-index gradient writes (rs_item_grad_marked) so the optimizer can skip the

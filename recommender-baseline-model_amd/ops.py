@@ -759,9 +759,11 @@ def item_index_view(nsrc, rows, table_rows, d, ws):
     return sk, sv, start, int(out[3])
 
 
-def item_grad(ws, nsrc, rows, dx, scale, drop_p, salt, seed_base, f, w1, w2, dtable, marks=None):
-    """marks: (row_marks u8 [table_rows], epoch u8 [1]) -- rs_item_grad_marked stamps the rows it writes (bf16)."""
-    table_rows, d = dtable.shape
+def item_grad(ws, nsrc, rows, dx, scale, drop_p, salt, seed_base, f, w1, w2, dtable, marks=None, table_rows=None):
+    """marks: (row_marks u8 [table_rows], epoch u8 [1]) -- rs_item_grad_marked stamps the rows it writes (bf16).
+    table_rows: the key range the index was built with, where that is not the table's row count."""
+    d = dtable.shape[1]
+    table_rows = dtable.shape[0] if table_rows is None else table_rows
     if marks is not None and dx.dtype != torch.float32:
         call("rs_item_grad_marked", ptr(ws), nsrc, rows, table_rows, d, ptr(dx), scale, drop_p, salt, ptr(seed_base),
              ptr(f) if f is not None else None, ptr(w1) if w1 is not None else None,
@@ -846,6 +848,56 @@ def sas_ce_rows_bwd(slab, splits, cap, rank, x, ln_w, mean, rstd, dx, part):
     assert dx.shape == (M, d) and rank.numel() >= M
     call("rs_sas_ce_rows_bwd", dtype_code(x), M, d, ptr(slab), splits, cap, ptr(rank), ptr(x), ld(x), ptr(ln_w),
          ptr(mean), ptr(rstd), ptr(dx), ld(dx), ptr(part), stream())
+
+
+# ---- SAS sampled-softmax head over batch-shared candidates (sas_sce.hip) --------------------
+def sas_sce_max_k():
+    """Most candidates the sampled-softmax head takes (host only)."""
+    return int(_lib.lib().rs_sas_sce_max_k())
+
+
+def sas_sce_ok(d, dtype):
+    """The dtypes / widths rs_sas_sce_fwd / _bwd cover: fp32 at any d <= 1024, bf16 at d % 8 == 0, d <= 1024 (the
+    MFMA sweep up to d = 128, a plain kernel past it)."""
+    return d <= 1024 and (dtype == torch.float32 or (dtype == torch.bfloat16 and d % 8 == 0))
+
+
+def sas_sce_ws_numel(cap, K, d):
+    """fp32 elements of the head's workspace (lse, z0, the dEc split slabs): a function of (cap, K, d) alone."""
+    n = int(_lib.lib().rs_sas_sce_ws_bytes(cap, K, d))
+    if n < 0:
+        raise RuntimeError("rs_sas_sce_ws_bytes: bad arguments")
+    return n // 4
+
+
+def sas_sce_dh_splits(cap, K, d):
+    """Slabs rs_sas_sce_bwd writes dh in (one per split of the candidates; host only)."""
+    return int(_lib.lib().rs_sas_sce_dh_splits(cap, K, d))
+
+
+def sas_sce_fwd(hl, lab, count, cap, E, cand, divisor, ws, out):
+    """lse / z0 per compact row into ws, out = {loss sum, valid rows, sum / divisor} (rs_sas_sce_fwd)."""
+    d, K = hl.shape[1], cand.numel()
+    assert hl.shape[0] >= cap and lab.numel() >= cap and E.dtype == hl.dtype and E.shape[1] == d and E.is_contiguous()
+    assert cand.dtype == torch.int64 and cand.is_contiguous() and ws.numel() >= sas_sce_ws_numel(cap, K, d)
+    call("rs_sas_sce_fwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), E.shape[0], ptr(cand),
+         K, ptr(divisor), ptr(ws), ptr(out), stream())
+
+
+def sas_sce_bwd(hl, lab, count, cap, E, cand, divisor, dloss, ws, dh, coef, pg, dEc, keys=None):
+    """dh fp32 [sas_sce_dh_splits][cap][d], coef [cap], pg = coef * hl [cap][d], dEc fp32 [K][d], keys int64
+    [cap + K] (rs_sas_sce_bwd)."""
+    d, K = hl.shape[1], cand.numel()
+    assert dh.numel() >= sas_sce_dh_splits(cap, K, d) * cap * d and coef.numel() >= cap and pg.numel() >= cap * d and dEc.numel() >= K * d
+    assert keys is None or (keys.numel() >= cap + K and keys.dtype == torch.int64)
+    assert ws.numel() >= sas_sce_ws_numel(cap, K, d) and E.shape[1] == d and E.is_contiguous()
+    call("rs_sas_sce_bwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), E.shape[0], ptr(cand),
+         K, ptr(divisor), ptr(dloss), ptr(ws), ptr(dh), ptr(coef), ptr(pg), ptr(dEc), ptr(keys), stream())
+
+
+def uniform_items(seed_base, salt, item_num, out):
+    """out (int64, device): uniform draws with replacement over [1, item_num] from (seed_base, salt)."""
+    call("rs_uniform_items", ptr(seed_base), salt, item_num, out.numel(), ptr(out), stream())
 
 
 def sas_head_finish(part, divisor, out):

@@ -165,7 +165,9 @@ class FusedTrainStep:
         (sizes the compacted vocabulary-logit buffers; default B*T).
         loss (SAS): "bce" (the reference's sampled objective) or "ce" (softmax cross-entropy over the whole
         catalogue with the item table as output layer, SASModel.ce_loss); None = the model's args.sas_loss.  With
-        "ce" the batch's neg plays no part and may be None; single device only.
+        "ce" the batch's neg plays no part and may be None; single device only.  "sampled_ce": the same softmax over
+        the positive and K candidates shared by the whole batch (SASModel.sampled_ce_loss); the batch is (seq, pos,
+        cand) with cand int64 (K,); single device, steps_per_graph = 1.
         overlap (DP, default on unless bucket_numel is given): each gradient bucket's all-reduce starts as soon as the backward has finished it (dp.BucketedExchange);
         bucket_numel: otherwise ONE all-reduce after the backward, in buckets of that many floats.
         vocab_shard (BERT, DP): out.weight / out.bias sharded over the ranks (rbm_amd.vocab_parallel).
@@ -182,13 +184,13 @@ class FusedTrainStep:
         if loss is None:
             loss = getattr(model.sas, "sas_loss", "bce") if self.kind == "sas" else None
         if self.kind == "sas":
-            if loss not in ("bce", "ce"):
-                raise ValueError(f"loss must be 'bce' or 'ce', got {loss!r}")
+            if loss not in ("bce", "ce", "sampled_ce"):
+                raise ValueError(f"loss must be 'bce', 'ce' or 'sampled_ce', got {loss!r}")
         elif loss is not None:
             raise ValueError(f"loss={loss!r} needs a SAS model (the BERT step has one objective)")
         self.loss = loss
-        if loss == "ce" and (dpx.world() > 1 if dp is None else bool(dp)):
-            raise ValueError("FusedTrainStep(loss='ce') runs on a single device (data parallel is not covered)")
+        if loss in ("ce", "sampled_ce") and (dpx.world() > 1 if dp is None else bool(dp)):
+            raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
         self.engine = model.sas.engine() if self.kind == "sas" else model.engine()
         self.flat = self.engine.flat
         self.engine.sync_compute_weights()
@@ -289,10 +291,12 @@ class FusedTrainStep:
         # which stamp the rows they write; the optimizer then reads the gradient of those rows only (4 of its 30
         # bytes per element elsewhere).  Not under data parallel (other ranks' rows arrive by the exchange) nor
         # with the l2 regulariser (it writes every row); tables below ROW_MARKS_MIN rows are mostly touched.
-        # Nor with the full-catalogue CE loss: every table row then has a non-zero gradient.
-        if self.loss == "ce":
+        # Nor with the full-catalogue CE loss: every table row then has a non-zero gradient.  The sampled softmax's
+        # gradient is sparse again, but its head rows come from the fp32 index launch, which stamps nothing: off too.
+        if self.loss in ("ce", "sampled_ce"):
             self.engine.row_marks = None
-        if (not self.dp and not self.l2 and self.loss != "ce" and os.environ.get("RS_ROW_MARKS", "1") != "0"
+        if (not self.dp and not self.l2 and self.loss not in ("ce", "sampled_ce")
+                and os.environ.get("RS_ROW_MARKS", "1") != "0"
                 and hasattr(self.engine, "enable_row_marks")):
             r = self.engine.enable_row_marks(self.ROW_MARKS_MIN)
             if r is not None:
@@ -391,6 +395,11 @@ class FusedTrainStep:
             seq, pos = batch[0], batch[1]
             saved = eng.ce_forward(seq, pos, True, self.loss_out, max_labelled=self.max_labelled, clone_seed=False)
             eng.ce_backward(saved, self.flat.grad)
+        elif self.kind == "sas" and self.loss == "sampled_ce":
+            seq, pos, cand = batch
+            saved = eng.sce_forward(seq, pos, cand, True, self.loss_out, max_labelled=self.max_labelled,
+                                    clone_seed=False)
+            eng.sce_backward(saved, self.flat.grad)
         elif self.kind == "sas":
             seq, pos, neg = batch
             pl, nl, saved = eng.forward(seq, pos, neg, True, clone_seed=False, fuse_head=eng.fused_head,
@@ -723,6 +732,9 @@ class FusedTrainStep:
         S = int(steps_per_graph)
         if S < 1:
             raise ValueError("steps_per_graph must be >= 1")
+        if S > 1 and self.loss == "sampled_ce":
+            raise ValueError("loss='sampled_ce' needs steps_per_graph = 1: cand has another shape than seq / pos, "
+                             "and the unrolled graph takes one packed buffer")
         if S > 1 and self.dp and not self.graph_collectives:
             raise ValueError("steps_per_graph > 1 under DP needs the all-reduce inside the graph (graph_collectives)")
         self.steps_per_graph = S
@@ -962,8 +974,17 @@ class FusedTrainStep:
         S = self._unroll_check(steps_per_graph)
         self.sampler = sampler
         shape = (sampler.batch_size, sampler.max_len)
-        self.packed = torch.zeros((want,) + shape, dtype=torch.int64, device=self.flat.device)
-        self.static = list(self.packed.unbind(0))
+        if self.loss == "sampled_ce":
+            K = getattr(sampler, "shared_negs", None)
+            if not K:
+                raise ValueError("loss='sampled_ce' needs a sampler with shared_negs=K")
+            # no packed buffer: cand has another shape (replay_packed then goes through replay(), as after capture()
+            # with inputs of different shapes)
+            self.packed = None
+            self.static = [torch.zeros(n, dtype=torch.int64, device=self.flat.device) for n in (shape, shape, (K,))]
+        else:
+            self.packed = torch.zeros((want,) + shape, dtype=torch.int64, device=self.flat.device)
+            self.static = list(self.packed.unbind(0))
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

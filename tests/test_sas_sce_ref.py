@@ -1,0 +1,182 @@
+"""CPU checks of the SASRec sampled softmax over batch-shared candidates (no GPU): the float64 reference against the
+plain-torch spelling and against the full-catalogue cross-entropy reference, the defined edge cases, the public switch
+as far as it runs without a device, and the host-only parts of the C ABI."""
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import sas_ce_ref as ce_ref
+import sas_sce_ref as ref
+from test_sas_ce_ref import HEADER, batch, params, sas_args
+
+NEW = ["rs_sas_sce_fwd", "rs_sas_sce_bwd", "rs_sas_sce_ws_bytes", "rs_sas_sce_dh_splits", "rs_sas_sce_max_k",
+       "rs_uniform_items"]
+
+
+def _close(a, b, tol=1e-12):
+    return torch.linalg.norm(a - b) <= tol * max(torch.linalg.norm(b).item(), 1e-30)
+
+
+@pytest.mark.parametrize("V,T,d,L,h,B,K", [(60, 16, 64, 2, 1, 4, 1), (60, 16, 64, 2, 1, 4, 23), (37, 9, 50, 1, 2, 2, 90)])
+def test_reference_matches_the_plain_torch_spelling(V, T, d, L, h, B, K):
+    P = params(V, T, d, L, h)
+    rng = np.random.default_rng(V + K)
+    seq, pos = batch(rng, B, T, V)
+    cand = torch.from_numpy(rng.integers(0, V + 1, K))            # zeros, duplicates and hits of positives included
+    loss, g = ref.sce_loss_and_grads(P, seq, pos, cand, L, h)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in P.items()}
+    want = ref.torch_definition(leaves, seq, pos, cand, L, h)
+    want.backward()
+    assert abs(loss.item() - want.item()) <= 1e-12 * abs(want.item())
+    for k, v in leaves.items():
+        w = v.grad if v.grad is not None else torch.zeros_like(v)
+        assert _close(g[k], w), k
+    assert not g["sas.item_emb.weight"][0].any()
+
+
+@pytest.mark.parametrize("V,T,d,L,h,B", [(60, 16, 64, 2, 1, 4), (37, 9, 50, 1, 2, 2)])
+def test_all_items_as_candidates_is_the_full_cross_entropy(V, T, d, L, h, B):
+    """cand = 1..V against sas_ce_ref.ce_loss, loss and gradients to 1e-12 relative.  The positive's own duplicate is
+    masked and every other item is live, so the two softmaxes run over the same item classes; the full CE has one
+    class more, the padding row 0, whose logit <f, 0> is exactly 0: ce_r = log(exp(lse_r) + exp(0)) - z_r0 =
+    logaddexp(lse_r, 0) - z_r0 with lse_r the sampled loss' own log-sum.  That one term is put back here in closed form
+    (at these shapes it is 2e-8 of the loss: without it the identity holds to 1e-9, not 1e-12)."""
+    P = params(V, T, d, L, h)
+    seq, pos = batch(np.random.default_rng(V), B, T, V)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in P.items()}
+    f = ref.osas.log2feats(leaves, seq, L, h)
+    lse, z0, valid = ref.sce_rows(f, leaves["sas.item_emb.weight"], pos, torch.arange(1, V + 1), ref.osas.Exact())
+    assert abs(((lse - z0) * valid).sum().item() / int(valid.sum())
+               - ref.sce_loss(P, seq, pos, torch.arange(1, V + 1), L, h).item()) < 1e-13
+    loss = ((torch.logaddexp(lse, torch.zeros_like(lse)) - z0) * valid).sum() / int(valid.sum())
+    loss.backward()
+    want, gw = ce_ref.ce_loss_and_grads(P, seq, pos, L, h)
+    assert abs(loss.item() - want.item()) <= 1e-12 * abs(want.item())
+    for k, v in leaves.items():
+        assert _close(v.grad if v.grad is not None else torch.zeros_like(v), gw[k]), k
+    # and the class-0 term is all that separates the two losses
+    plain = ref.sce_loss(P, seq, pos, torch.arange(1, V + 1), L, h).item()
+    gap = ((torch.logaddexp(lse, torch.zeros_like(lse)) - lse) * valid).sum().item() / int(valid.sum())
+    assert 0 < want.item() - plain and abs((want.item() - plain) - gap) <= 1e-12 * abs(want.item())
+
+
+def test_duplicates_count_and_zero_slots_do_not():
+    V, T, d, L, h = 30, 8, 64, 1, 1
+    P = params(V, T, d, L, h)
+    seq, pos = batch(np.random.default_rng(1), 2, T, V)
+    f = ref.osas.log2feats(P, seq, L, h).reshape(-1, d)
+    E = P["sas.item_emb.weight"]
+    tgt = pos.reshape(-1)
+    free = next(v for v in range(1, V + 1) if v not in set(tgt.tolist()))    # no row's positive
+    base = ref.sce_loss(P, seq, pos, torch.tensor([free]), L, h)
+    twice = ref.sce_loss(P, seq, pos, torch.tensor([free, free]), L, h)
+    padded = ref.sce_loss(P, seq, pos, torch.tensor([0, free, 0, 0]), L, h)
+    valid = tgt != 0
+    z0, zf = (f * E[tgt]).sum(-1), f @ E[free]
+    want1 = (torch.log(z0.exp() + zf.exp()) - z0)[valid].mean()
+    want2 = (torch.log(z0.exp() + 2 * zf.exp()) - z0)[valid].mean()
+    assert abs(base.item() - want1.item()) < 1e-12 and abs(twice.item() - want2.item()) < 1e-12
+    assert abs(padded.item() - base.item()) < 1e-12          # the same classes, summed in another order
+
+
+def test_a_row_without_a_live_candidate_and_an_all_padding_batch():
+    V, T, d, L, h = 30, 8, 64, 1, 1
+    P = params(V, T, d, L, h)
+    seq = torch.zeros(1, T, dtype=torch.int64)
+    pos = torch.zeros(1, T, dtype=torch.int64)
+    seq[0, -2:] = torch.tensor([3, 4])
+    pos[0, -2:] = torch.tensor([7, 7])
+    # every candidate is 0 or the rows' own positive: nothing is live, loss 0, gradient 0
+    loss, g = ref.sce_loss_and_grads(P, seq, pos, torch.tensor([7, 0, 7]), L, h)
+    assert loss.item() == 0.0 and all(not v.any() for v in g.values())
+    z = torch.zeros(2, T, dtype=torch.int64)
+    loss, g = ref.sce_loss_and_grads(P, z, z, torch.tensor([5, 6]), L, h)
+    assert loss.item() == 0.0 and all(not v.any() for v in g.values())
+
+
+def test_head_references_agree_with_torch_autograd():
+    rng = np.random.default_rng(0)
+    cap, count, d, V, K = 40, 33, 64, 50, 70
+    hl, E = rng.standard_normal((cap, d)) * 0.3, rng.standard_normal((V + 1, d)) * 0.3
+    E[0] = 0
+    lab, cand = rng.integers(1, V + 1, cap), rng.integers(0, V + 1, K)
+    lse, z0, out = ref.head_fwd_ref(hl, lab, count, E, cand, float(count))
+    ht, Et = torch.from_numpy(hl[:count]).requires_grad_(True), torch.from_numpy(E).requires_grad_(True)
+    R = ref.osas.Exact()
+    loss = ref.sce_from_feats(ht[None], Et, torch.from_numpy(lab[:count])[None], torch.from_numpy(cand), R)
+    assert abs(out[2] - loss.item()) < 1e-12 and out[1] == count
+    loss.backward()
+    dh, coef, pg, dEc, keys, _ = ref.head_bwd_ref(hl, lab, count, E, cand, float(count))
+    assert np.abs(dh - ht.grad.numpy()).max() < 1e-13
+    dE = np.zeros_like(E)
+    np.add.at(dE, keys[:count], pg)
+    np.add.at(dE, keys[cap:], dEc)
+    dE[0] = 0                                                     # key 0: no table row
+    assert np.abs(dE - Et.grad.numpy()).max() < 1e-13
+    assert not keys[count:cap].any()
+
+
+def test_model_factory_takes_the_switch_and_needs_a_positive_k():
+    import rbm_amd  # noqa: F401
+    from rbm_amd.models import model_factory
+    from rbm_amd.models.sas_model.sas import SAS_LOSSES
+    assert SAS_LOSSES == ("bce", "ce", "sampled_ce")
+    m = model_factory(sas_args(sas_loss="sampled_ce", sas_shared_negs=64))
+    assert m.sas.sas_loss == "sampled_ce" and m.sas.sas_shared_negs == 64
+    for bad in ({}, {"sas_shared_negs": 0}, {"sas_shared_negs": None}, {"sas_shared_negs": -3}):
+        with pytest.raises(ValueError, match="sas_shared_negs"):
+            model_factory(sas_args(sas_loss="sampled_ce", **bad))
+    assert callable(model_factory(sas_args()).sampled_ce_loss)    # whatever sas_loss says
+    z = np.zeros((1, 16), np.int64)
+    with pytest.raises(RuntimeError):                             # no CPU fallback: the engine needs a device
+        m.sampled_ce_loss(z, z, np.arange(1, 5))
+
+
+def test_fused_train_step_validates_before_touching_a_device():
+    import rbm_amd  # noqa: F401
+    from rbm_amd.models import model_factory
+    from rbm_amd.train_step import FusedTrainStep
+    with pytest.raises(ValueError, match="single device"):
+        FusedTrainStep(model_factory(sas_args()), loss="sampled_ce", dp=True)
+    with pytest.raises(ValueError, match="single device"):
+        FusedTrainStep(model_factory(sas_args(sas_loss="sampled_ce", sas_shared_negs=8)), dp=True)
+
+
+def test_header_declares_and_lib_binds_the_head():
+    syms = set(re.findall(r"^(?:int|int64_t) (rs_\w+)\(", open(HEADER).read(), flags=re.M))
+    import rbm_amd._lib as L
+    from rbm_amd import ops
+    for s in NEW:
+        assert s in syms, s
+        assert s in L.SIGNATURES, s
+    assert L.RESTYPES["rs_sas_sce_ws_bytes"] is L.C.c_int64
+    for name in ("sas_sce_fwd", "sas_sce_bwd", "sas_sce_ws_numel", "sas_sce_max_k", "uniform_items"):
+        assert callable(getattr(ops, name))
+    assert L.lib().rs_abi_version() == 1
+
+
+def test_workspace_is_sized_by_cap_k_d_alone():
+    """By signature the sizing function cannot see V; the engine's index workspace is sized through the item index's
+    own function, whose key range sas.py pins at or above SCE_INDEX_ROWS: equal for any two V below it."""
+    import rbm_amd._lib as L
+    from rbm_amd import ops
+    from rbm_amd.models.sas_model.sas import SCE_INDEX_ROWS
+    assert len(L.SIGNATURES["rs_sas_sce_ws_bytes"]) == 3
+    assert ops.sas_sce_max_k() >= 16384
+    for cap, K, d in [(1, 1, 64), (1031, 257, 128), (25600, 4096, 64), (6400, 16384, 128)]:
+        n = ops.sas_sce_ws_numel(cap, K, d)
+        assert n >= 2 * cap and n == ops.sas_sce_ws_numel(cap, K, d)
+        a, b = (ops.item_index_ws_bytes(1, cap + K, max(V + 1, SCE_INDEX_ROWS), d) for V in (1000, 30000))
+        assert a == b
+
+
+def test_uniform_items_restatement_is_uniform_and_seeded():
+    a = ref.uniform_items_ref(5, 1234, 50, 4000)
+    assert a.min() >= 1 and a.max() <= 50
+    assert (a == ref.uniform_items_ref(5, 1234, 50, 4000)).all()
+    assert (a != ref.uniform_items_ref(6, 1234, 50, 4000)).any() and (a != ref.uniform_items_ref(5, 1235, 50, 4000)).any()
+    n, q = 4000, 1 / 50
+    sigma = np.sqrt(n * q * (1 - q))
+    assert np.abs(np.bincount(a, minlength=51)[1:] - n * q).max() <= 6 * sigma
