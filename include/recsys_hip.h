@@ -340,7 +340,9 @@ int rs_vocab_ce_bwd(int64_t R, int64_t V1, int64_t d, const void* h, int64_t ldh
  * 256- (fwd) / 128-entry (bwd) tile of E in LDS and walks every 128-row tile of h against it, so E streams
  * from HBM once and the short d-deep products run back to back instead of one cold tile at a time.
  * rs_vocab_head_fwd: out = {loss sum, labelled count, sum / (count_override or count)}, ws keeps lse.
- * rs_vocab_head_bwd: dlogits [R][V1] bf16 (rows < live count) = (softmax - onehot) * (dloss or 1) / count. */
+ * rs_vocab_head_bwd: dlogits [R][V1] bf16 (rows < live count) = (softmax - onehot) * (dloss or 1) / count;
+ *   its 16-byte stores may zero a written row's pad columns from V1 to the next multiple of 8 (rs_vocab_ce_bwd
+ *   leaves them alone). */
 int rs_vocab_head_supported(int64_t d);
 int rs_vocab_head_fwd(int64_t R, int64_t V1, int64_t d, const void* h, int64_t ldh, const void* E, int64_t lde,
                       const float* bias, const int64_t* labels, const int* rows_dev, const float* count_override,
@@ -641,7 +643,10 @@ int rs_sas_head_fwd(int64_t M, int64_t d, const void* x, const float* ln_w, cons
 /* Backward: with dpl_in == NULL the BCE gradient is formed here: dpl = (sigmoid(pl)-1)/c,
  * dnl = sigmoid(nl)/c on valid rows, c = *divisor or the forward's valid count, written to
  * dpl/dnl, and out[0..3] = {loss sum, count, mean loss (as rs_bce_fwd), neg-term sum}; with
- * dpl_in/dnl_in given (autograd) those are used.  Then df = dpl E[pos] + dnl E[neg] and
+ * dpl_in/dnl_in given (autograd) those are used and part, out, dpl, dnl are left alone.  A batch
+ * without a valid row (count 0): dpl, dnl, dx and lnpart are exactly zero, out[0] = out[1] =
+ * out[3] = 0 and out[2] = 0/c -- NaN without a divisor (the reference's mean over an empty
+ * selection, as rs_bce_fwd), 0 with one.  Then df = dpl E[pos] + dnl E[neg] and
  * dx = LN'(x, df) (bf16); lnpart[b][2][d] = LN affine partials (reduce with rs_reduce_segments).
  * The item-table gradient of the logits is left to rs_item_grad. */
 int rs_sas_head_bwd(int64_t M, int64_t d, const float* part, const float* divisor, float* out, const float* pl,

@@ -30,6 +30,24 @@ def _inputs(M, V1, d, seed):
     return ids, pos, neg, dx, f, dpl, dnl
 
 
+def _table_f64(base, ids, pos, neg, dx, f, dpl, dnl, scale, p, salt, seed_base):
+    """float64 table gradient on top of base; at p > 0 the embedding rows carry the dropout site's keep mask (the
+    kernels' own hash through rs_dropout_rowmask, element index row * d + column) times 1 / (1 - p) in float32"""
+    from rbm_amd import ops
+    mk = 1.0
+    if p > 0:
+        ones = torch.ones(dx.shape, dtype=torch.float32, device="cuda")
+        kept = torch.empty_like(ones)
+        ops.dropout_rowmask(ones, p, salt, seed_base, None, kept)
+        mk = (kept > 0).double() * float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+    t = base.double().clone()
+    for k, w, src in ((ids, None, dx), (pos, dpl, f), (neg, dnl, f)):
+        rows = src.double() * (scale * mk if w is None else w.double()[:, None])
+        keep = k != 0
+        t.index_add_(0, k[keep], rows[keep])
+    return t
+
+
 def _radix_path(M, V1):
     """True when itemgrad.hip's layout() takes the hand-written radix sort instead of the counting sort: tables
     over the LDS histogram's 32k rows, (512-entry sort blocks) x (table rows) > 2^26 histogram ints, or keys wider
@@ -64,13 +82,8 @@ def test_item_grad_matches_atomic_scatter(M, V1, d, p):
     torch.cuda.synchronize()
     assert rel(ours.cpu().numpy(), ref.cpu().numpy()) < 1e-5
     assert torch.equal(ours[0], base[0])                         # padding row untouched
-    if p == 0.0:
-        t = base.double().clone()
-        for k, w, src in ((ids, None, dx), (pos, dpl, f), (neg, dnl, f)):
-            rows = src.double() * (scale if w is None else w.double()[:, None])
-            keep = k != 0
-            t.index_add_(0, k[keep], rows[keep])
-        assert rel(ours.cpu().numpy(), t.cpu().numpy()) < 1e-5
+    t = _table_f64(base, ids, pos, neg, dx, f, dpl, dnl, scale, p, salt, seed_base)
+    assert rel(ours.cpu().numpy(), t.cpu().numpy()) < 1e-5
     # reproducible bit for bit
     again = base.clone()
     ops.item_index_build([ids, pos, neg], V1, d, ws)
@@ -152,13 +165,8 @@ def test_item_grad_f32_matches_atomic_scatter(M, V1, d, p):
     torch.cuda.synchronize()
     assert rel(ours.cpu().numpy(), ref.cpu().numpy()) < 1e-5   # both fp32 sums, different orders
     assert torch.equal(ours[0], base[0])                         # padding row untouched
-    if p == 0.0:
-        t = base.double().clone()
-        for k, w, src in ((ids, None, dx), (pos, dpl, f), (neg, dnl, f)):
-            rows = src.double() * (scale if w is None else w.double()[:, None])
-            keep = k != 0
-            t.index_add_(0, k[keep], rows[keep])
-        assert rel(ours.cpu().numpy(), t.cpu().numpy()) < 1e-5
+    t = _table_f64(base, ids, pos, neg, dx, f, dpl, dnl, scale, p, salt, seed_base)
+    assert rel(ours.cpu().numpy(), t.cpu().numpy()) < 1e-5
     again = base.clone()
     ops.item_index_build([ids, pos, neg], V1, d, ws)
     ops.item_grad(ws, 3, M, dx, scale, p, salt, seed_base, f, dpl, dnl, again)
