@@ -158,8 +158,8 @@ int rs_attn_fwd(int dtype, int64_t B, int64_t T, int64_t H, int64_t Dh, const vo
                 float scale, int mask_kind, const int64_t* ids, float drop_p, uint64_t seed,
                 const uint64_t* seed_base, void* stream);
 /* Backward: dq, dk, dv (overwritten).  ws: >= B*H*T floats (row deltas).  mask_kind | RS_ATTN_DELTA_IN: ws
- * already holds delta[(b*H+h)*T + t] = rowsum(dO * O) over the head's columns (rs_sas_block_out_bwd with o given
- * forms it); the bf16 LDS path then reads neither O nor recomputes it (other paths recompute it into ws). */
+ * already holds delta[(b*H+h)*T + t] = rowsum(dO * O) over the head's columns (rs_sas_block_out_bwd_delta with o
+ * and delta given forms it); the bf16 LDS path then reads neither O nor recomputes it (other paths recompute it into ws). */
 #define RS_ATTN_DELTA_IN 0x100
 /* delta[(b*H+h)*T + t] = rowsum over head h's Dh columns of dout * o (values as stored; dtype as rs_attn_bwd) --
  * the RS_ATTN_DELTA_IN input when no fused kernel forms it (BERT: after the output projection's input gradient,
@@ -410,48 +410,207 @@ int rs_graph_upload(void* graph_exec, void* stream);
  * Same outputs, saved tensors and dropout masks as the unfused kernel sequence, so rs_* backward
  * kernels consume them unchanged.
  *
- * Replaces, for SASRec block i (BS/models/sas_model/sas.py:73-76, the attention input side):
- *   Q = LN1(x) [mean/rstd saved];  q = Q Wq^T + bq;  kv = x Wkv^T + bkv   (kv: [M][2d])
- * Wq = in_proj_weight[:d], Wkv = in_proj_weight[d:] (bf16, torch [out][in] layout).
- * Returns RS_ERR_UNSUPPORTED for other d: callers fall back to the unfused sequence. */
-int rs_sas_block_in(int64_t M, int64_t d, const void* x, int64_t ldx, const float* ln_w, const float* ln_b,
-                    float eps, void* Q, float* mean, float* rstd, const void* Wq, const float* bq, void* q,
-                    const void* Wkv, const float* bkv, void* kv, void* stream);
-/* The first block's input side with the embedding stage folded in (rowchain: one launch instead of two): x0 =
- * (item_emb[ids]*scale + pos_emb[t]) -> dropout(p, salt) -> *(ids != 0), exactly as rs_embed_fwd mode 0, stored
- * to x0 [M][d] and fed to rs_sas_block_in's chain; with count_ids, count_parts[rs_sas_block_in_count_parts(M)]
- * (int32) receives per-workgroup counts of count_ids != 0 (the BCE divisor for rs_sas_block_out_head).  d in {64, 128}
- * and 16-byte aligned tables / x0, else RS_ERR_ARG. */
-int64_t rs_sas_block_in_count_parts(int64_t M);
-int rs_sas_block_in_embed(int64_t M, int64_t d, const int64_t* ids, int64_t T, const void* item_emb, const void* pos_emb,
-                          float scale, float drop_p, uint64_t salt, const uint64_t* seed_base, void* x0,
-                          const int64_t* count_ids, int* count_parts, const float* ln_w, const float* ln_b, float eps,
-                          void* Q, float* mean, float* rstd, const void* Wq, const float* bq, void* q, const void* Wkv,
-                          const float* bkv, void* kv, void* stream);
-/* The output side (sas.py:75-84, PointWiseFeedForward sas.py:8-24):
+ * Each entry takes the width d, one or two of the argument structs below and the stream.  The structs ARE the
+ * kernels' arguments (field order = kernel-argument layout; rs_abi_sizeof reports their sizes).  An entry checks its
+ * arguments first (RS_ERR_ARG for a bad value, RS_ERR_UNSUPPORTED for d not in {64, 128}: callers fall back to the
+ * unfused sequence) and launches nothing in that case; otherwise it copies the structs BY VALUE into the launch and
+ * keeps no pointer to them once it returns (a captured graph replays the copy; the caller may free or reuse the
+ * struct at once).  Fields an entry fills itself are marked "set by ..." and are ignored in the caller's struct.
+ * [M][d] tensors are bf16, dense (row stride d) and 16-byte aligned unless a stride is named; LayerNorm
+ * parameters, biases and row statistics are fp32. */
+#ifdef __HIPCC__
+typedef __bf16 rs_bf16;
+#else
+typedef uint16_t rs_bf16;
+#endif
+
+/* The embedding stage folded into the first block's input side: x0 = (item_emb[ids]*scale + pos_emb[t]) ->
+ * dropout(drop_p, salt) -> *(ids != 0), exactly as rs_embed_fwd mode 0. */
+typedef struct rs_sas_embed_args {
+  const int64_t* ids;          /* [M] item ids, M % T == 0 */
+  const rs_bf16* item_emb;     /* item table [rows][d], 16-byte aligned */
+  const rs_bf16* pos_emb;      /* positional table [T][d], 16-byte aligned */
+  int64_t T;                   /* sequence length (t = row % T) */
+  float scale;
+  float drop_p;
+  uint64_t salt;               /* dropout site salt */
+  const uint64_t* seed_base;   /* device step seed (nullable) */
+  rs_bf16* x0;                 /* [M][d] out: the embedding output (the backward's LN1 input), 16-byte aligned */
+  const int64_t* count_ids;    /* optional, with count_parts (both or neither): [M] ids to count != 0 */
+  int* count_parts;            /* [rs_sas_block_grid(M)] out: per-workgroup counts of count_ids != 0 (the BCE
+                                  divisor of rs_sas_head_args) */
+} rs_sas_embed_args;
+
+/* Block i's attention input side (BS/models/sas_model/sas.py:73-76):
+ *   Q = LN1(x) [mean/rstd saved];  q = Q Wq^T + bq;  kv = x Wkv^T + bkv */
+typedef struct rs_sas_in_args {
+  int64_t M;                   /* token rows */
+  const rs_bf16* x;            /* [M] rows at stride ldx; set by the entry to e.x0 (embed form) / the first struct's
+                                  xn (rs_sas_block_out_in) */
+  int64_t ldx;                 /* % 8 == 0; set by the entry to d where it sets x */
+  const float* ln_w;           /* LN1 affine [d] */
+  const float* ln_b;
+  float eps;
+  rs_bf16* Q;                  /* [M][d] out */
+  float* mean;                 /* [M] out */
+  float* rstd;                 /* [M] out */
+  const rs_bf16* Wq;           /* in_proj_weight[:d] (torch [out][in] layout) */
+  const float* bq;
+  rs_bf16* q;                  /* [M][d] out */
+  const rs_bf16* Wkv;          /* in_proj_weight[d:] */
+  const float* bkv;            /* [2d] */
+  rs_bf16* kv;                 /* [M][2d] out */
+  rs_sas_embed_args e;         /* e.item_emb == NULL: x is read; else the first block's embed form */
+} rs_sas_in_args;
+
+/* The SAS head riding in the LAST block's output side (token-local once the BCE divisor c = *divisor or the sum of
+ * count_parts is known): f = LN_last(xn) [saved], pl/nl = <f, E[pos]>/<f, E[neg]>, dpl = (sigmoid(pl)-1)/c,
+ * dnl = sigmoid(nl)/c on pos != 0 [saved], dx = LN_last'(xn, dpl E[pos] + dnl E[neg]). */
+typedef struct rs_sas_head_args {
+  const rs_bf16* E;            /* tied item table [rows][d] */
+  const int64_t* pos;          /* [M] */
+  const int64_t* neg;          /* [M] */
+  const float* ln_w;           /* last LayerNorm affine [d] */
+  const float* ln_b;
+  float eps;                   /* set by the entry to the block's eps */
+  const int* count_parts;      /* [ncount] valid-position counts (rs_sas_embed_args.count_parts), required */
+  int ncount;                  /* > 0 */
+  const float* divisor;        /* optional device scalar: replaces the summed count */
+  rs_bf16* f;                  /* [M][d] out */
+  float* pl;                   /* [M] out */
+  float* nl;
+  float* dpl;
+  float* dnl;
+  rs_bf16* dx;                 /* [M][d] out: dx_L for the blocks' backward.  rs_sas_block_out_head_bwd: the two-launch
+                                  path's scratch, not written (set to NULL) by the one-launch kernel and may be NULL
+                                  where rs_sas_block_boundary_fused */
+  float* lnpart;               /* [G][2][d] out: LN affine partials per workgroup, G = rs_sas_block_grid(M) */
+  float* part;                 /* [G][3] out: BCE partials (sum softplus(-pl), sum softplus(nl), count) for
+                                  rs_wgrad_grouped_pos_stats */
+} rs_sas_head_args;
+
+/* Block i's output side (sas.py:75-84, PointWiseFeedForward sas.py:8-24):
  *   x1 = Q + o Wo^T + bo;  z = LN2(x1);  h1 = relu(drop(z W1^T + b1, salt1));
  *   xn = (drop(h1 W2^T + b2, salt2) + z) * (ids != 0)
  * Dropout element index m*d + n, seeds eff_seed(salt, *seed_base) as rs_gemm's epilogue. */
-int rs_sas_block_out(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo, void* x1,
-                     const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
-                     const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
-                     const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2, const uint64_t* seed_base,
-                     void* stream);
-/* rs_sas_block_out for the LAST block with the SAS head riding in the same kernel (token-local once the BCE
- * divisor c = *divisor or the sum of count_parts[ncount] from rs_sas_block_in_embed is known): per token, after
- * xn: f = LN_last(xn) [saved], pl/nl = <f, E[pos]>/<f, E[neg]>, dpl = (sigmoid(pl)-1)/c, dnl = sigmoid(nl)/c on
- * pos != 0 [saved], dx = LN_last'(xn, dpl E[pos] + dnl E[neg]) [saved, bf16].  Per workgroup
- * (rs_sas_block_grid(M) of them): lnpart[b][2][d] LN affine partials, part[b][3] BCE partials (sum softplus(-pl),
- * sum softplus(nl), count) for rs_wgrad_grouped_pos_stats.  RS_ERR_UNSUPPORTED for d not in {64, 128}. */
+typedef struct rs_sas_out_args {
+  int64_t M;
+  const rs_bf16* o;            /* [M][d] attention output */
+  const rs_bf16* Q;            /* [M][d] rs_sas_in_args.Q (the residual) */
+  const rs_bf16* Wo;           /* out_proj.weight [d][d] */
+  const float* bo;
+  rs_bf16* x1;                 /* [M][d] out */
+  const float* ln_w;           /* LN2 affine [d] */
+  const float* ln_b;
+  float eps;
+  rs_bf16* z;                  /* [M][d] out */
+  float* mean;                 /* [M] out (LN2 statistics) */
+  float* rstd;
+  const rs_bf16* W1;           /* conv1.weight [d][d] */
+  const float* b1;
+  rs_bf16* h1;                 /* [M][d] out */
+  const rs_bf16* W2;           /* conv2.weight [d][d] */
+  const float* b2;
+  rs_bf16* xn;                 /* [M][d] out: the block's output */
+  const int64_t* ids;          /* [M] row mask */
+  float drop_p;
+  uint64_t salt1;
+  uint64_t salt2;
+  const uint64_t* seed_base;   /* device step seed (nullable) */
+  rs_sas_head_args h;          /* h.E == NULL: no head */
+} rs_sas_out_args;
+
+/* Backward of the output side (sas.py:75-84 reversed):
+ *   dzres = dxn*(ids!=0); dy2 = drop2(dzres) [out]; da1 = relu'(h1)*drop1(dy2 W2) [out];
+ *   dz = da1 W1 + dzres; dx1 = LN2'(x1, dz) [out]; dout = dx1 Wo [out]
+ * Replaces rs_dropout_rowmask + 3 rs_gemm dgrads + rs_layernorm_bwd of the unfused sequence.
+ * "set from out": rs_sas_block_out_head_bwd copies the field from its rs_sas_out_args. */
+typedef struct rs_sas_out_bwd_args {
+  int64_t M;
+  const rs_bf16* dxn;          /* [M][d] gradient at xn; set by the two-struct entries (the first chain's dx, NULL in
+                                  the one-launch kernels) */
+  const int64_t* ids;          /* set from out */
+  const rs_bf16* h1;           /* set from out */
+  const rs_bf16* x1;           /* set from out */
+  const float* mean2;          /* LN2 statistics; set from out (mean, rstd) */
+  const float* rstd2;
+  const float* ln_w;           /* LN2 weight; set from out */
+  const rs_bf16* W2T;          /* TRANSPOSED weights ([in][out], rs_transpose_bf16); current when the launch runs */
+  const rs_bf16* W1T;
+  const rs_bf16* WoT;
+  rs_bf16* dy2;                /* [M][d] out */
+  rs_bf16* da1;
+  rs_bf16* dx1;
+  rs_bf16* dout;
+  float* part;                 /* [G][2][d] out: LN2 dgamma / dbeta partial set per workgroup, G =
+                                  rs_sas_block_grid(M); sum them with rs_reduce_segments / rs_wgrad_grouped (stride
+                                  2d, splits G) */
+  float drop_p;                /* set from out, with salt1, salt2, seed_base */
+  uint64_t salt1;
+  uint64_t salt2;
+  const uint64_t* seed_base;
+  const rs_bf16* o;            /* optional, with delta (both or neither): the attention output [M][d], one head; set
+                                  from out (where delta is given) */
+  float* delta;                /* [M] out: rowsum(dout * o), the attention backward's row term, so rs_attn_bwd
+                                  (mask_kind | RS_ATTN_DELTA_IN, ws = delta) neither reads o nor recomputes it */
+} rs_sas_out_bwd_args;
+
+/* Backward of the input side (sas.py:73-76 reversed):
+ *   dQ = dq Wq + dx1;  dx = dk Wk + dv Wv + LN1'(x, dQ) [out] */
+typedef struct rs_sas_in_bwd_args {
+  int64_t M;
+  const rs_bf16* dq;           /* [M][d] */
+  const rs_bf16* dkv;          /* [M][2d] */
+  const rs_bf16* dx1;          /* [M][d] rs_sas_out_bwd_args.dx1 (the residual's gradient) */
+  const rs_bf16* x;            /* [M][d] the block's input */
+  const float* mean1;          /* LN1 statistics */
+  const float* rstd1;
+  const float* ln_w;           /* LN1 weight */
+  const rs_bf16* WinT;         /* in_proj_weight^T [d][ldwt] */
+  int64_t ldwt;                /* must be 3d (RS_ERR_ARG otherwise) */
+  rs_bf16* dx;                 /* [M][d] out.  rs_sas_block_in_out_bwd: the two-launch path's scratch, not written (set
+                                  to NULL) by the one-launch kernel and may be NULL where rs_sas_block_boundary_fused */
+  float* part;                 /* [G][2][d] out: LN1 affine partials, as rs_sas_out_bwd_args.part */
+} rs_sas_in_bwd_args;
+
+/* Workgroups the row-chain kernels launch for M token rows = per-workgroup partial sets they write (0 for M <= 0). */
 int64_t rs_sas_block_grid(int64_t M);
-int rs_sas_block_out_head(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo,
-                          void* x1, const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
-                          const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
-                          const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2,
-                          const uint64_t* seed_base, const void* E, const int64_t* pos, const int64_t* neg,
-                          const float* lnl_w, const float* lnl_b, const int* count_parts, int64_t ncount,
-                          const float* divisor, void* f, float* pl, float* nl, float* dpl, float* dnl, void* dx,
-                          float* lnpart, float* part, void* stream);
+/* 1 where the two-struct entries below run their one-launch kernels: d in {64, 128} and every wave of the grid owns
+ * at most one 16-row tile (M <= 128 * CUs); they launch the two single-chain kernels on the stream otherwise. */
+int rs_sas_block_boundary_fused(int64_t M, int64_t d);
+
+/* The input side; with in->e.item_emb the first block's embed form (one launch instead of two; there d not in
+ * {64, 128} is RS_ERR_ARG). */
+int rs_sas_block_in(int64_t d, const rs_sas_in_args* in, void* stream);
+/* The output side; with out->h.E the LAST block's form with the head in the same kernel. */
+int rs_sas_block_out(int64_t d, const rs_sas_out_args* out, void* stream);
+/* The output side's backward; with out_bwd->o and out_bwd->delta also the attention backward's row term. */
+int rs_sas_block_out_bwd_delta(int64_t d, const rs_sas_out_bwd_args* out_bwd, void* stream);
+/* The same without o / delta, in the positional form its callers (and the kernel-level tests) use: the arguments are
+ * rs_sas_out_bwd_args' fields of the same names. */
+int rs_sas_block_out_bwd(int64_t M, int64_t d, const void* dxn, const int64_t* ids, const void* h1, const void* x1,
+                         const float* mean2, const float* rstd2, const float* ln_w, const void* W2T, const void* W1T,
+                         const void* WoT, void* dy2, void* da1, void* dx1, void* dout, float* part, float drop_p,
+                         uint64_t salt1, uint64_t salt2, const uint64_t* seed_base, void* stream);
+int rs_sas_block_in_bwd(int64_t d, const rs_sas_in_bwd_args* in_bwd, void* stream);
+/* Block-boundary launches: two adjacent row chains of the step in ONE launch, the tensor handed from the first to the
+ * second kept in registers.  Results are bitwise those of the two entries called back to back, for every M (both
+ * structs' M must agree).
+ *   rs_sas_block_out_in: rs_sas_block_out of block i (no head; every saved tensor still stored, xn included: it is
+ *     block i+1's saved input), then rs_sas_block_in(x = out->xn) of block i+1 (no embed form).
+ *   rs_sas_block_in_out_bwd: rs_sas_block_in_bwd of block i, then rs_sas_block_out_bwd_delta(dxn = in_bwd->dx) of block
+ *     i-1.  In the one-launch kernel dx is NOT written (RS_ERR_ARG if it is NULL and needed). */
+int rs_sas_block_out_in(int64_t d, const rs_sas_out_args* out, const rs_sas_in_args* in, void* stream);
+int rs_sas_block_in_out_bwd(int64_t d, const rs_sas_in_bwd_args* in_bwd, const rs_sas_out_bwd_args* out_bwd,
+                            void* stream);
+/* The forward/backward turnaround of the fused training step: rs_sas_block_out of the LAST block with its head
+ * (required) and, on the same rows, that block's rs_sas_block_out_bwd_delta(dxn = out->h.dx) in ONE launch: dx_L, h1, x1, o
+ * and the row statistics pass from the forward chain to the backward chain in registers.  Bitwise the two entries
+ * called back to back, for every M; every output of either is written except out->h.dx in the one-launch kernel
+ * (RS_ERR_ARG if it is NULL and needed).  Of out_bwd the caller gives M, W2T, W1T, WoT, dy2, da1, dx1, dout, part and
+ * delta (optional); the other fields are set from out. */
+int rs_sas_block_out_head_bwd(int64_t d, const rs_sas_out_args* out, const rs_sas_out_bwd_args* out_bwd,
+                              void* stream);
 
 /* Union-of-touched-rows exchange of an embedding-table gradient (sparse_rows.hip; data parallel,
  * replaces the dense all-reduce of the token / item table gradient -- the reference has no
@@ -467,81 +626,6 @@ int rs_rows_pack(const float* src, int64_t rows, int64_t d, const int32_t* index
                  float* compact, int64_t cap, void* stream);
 int rs_rows_unpack(float* dst, int64_t rows, int64_t d, const int32_t* index, const float* compact, void* stream);
 
-/* Number of LayerNorm affine partial sets the two backward kernels below write for M token rows
- * (one per workgroup). */
-int64_t rs_sas_block_parts(int64_t M);
-/* Backward of rs_sas_block_out (sas.py:75-84 reversed):
- *   dzres = dxn*(ids!=0); dy2 = drop2(dzres) [out]; da1 = relu'(h1)*drop1(dy2 W2) [out];
- *   dz = da1 W1 + dzres; dx1 = LN2'(x1, dz) [out]; dout = dx1 Wo [out];
- *   part[b][0][:] / part[b][1][:] = LN2 dgamma / dbeta partial set b (part >= 2*d*rs_sas_block_parts(M)
- *   floats; sum them with rs_reduce_segments / rs_wgrad_grouped: stride 2d, splits rs_sas_block_parts(M)).
- *   W*T are bf16 TRANSPOSED weights ([in][out], rs_transpose_bf16).
- * Replaces rs_dropout_rowmask + 3 rs_gemm dgrads + rs_layernorm_bwd of the unfused sequence. */
-int rs_sas_block_out_bwd(int64_t M, int64_t d, const void* dxn, const int64_t* ids, const void* h1, const void* x1,
-                         const float* mean2, const float* rstd2, const float* ln_w, const void* W2T, const void* W1T,
-                         const void* WoT, void* dy2, void* da1, void* dx1, void* dout, float* part, float drop_p,
-                         uint64_t salt1, uint64_t salt2, const uint64_t* seed_base, void* stream);
-/* rs_sas_block_out_bwd, and with o (the attention output [M][d] bf16, one head) also
- * delta[m] = rowsum(dout[m] * o[m]) -- the attention backward's row term, so rs_attn_bwd (mask_kind |
- * RS_ATTN_DELTA_IN, ws = delta) reads neither o nor recomputes it.  o and delta: both or neither. */
-int rs_sas_block_out_bwd_delta(int64_t M, int64_t d, const void* dxn, const int64_t* ids, const void* h1,
-                               const void* x1, const float* mean2, const float* rstd2, const float* ln_w,
-                               const void* W2T, const void* W1T, const void* WoT, void* dy2, void* da1, void* dx1,
-                               void* dout, float* part, float drop_p, uint64_t salt1, uint64_t salt2,
-                               const uint64_t* seed_base, const void* o, float* delta, void* stream);
-/* Backward of rs_sas_block_in (sas.py:73-76 reversed):
- *   dQ = dq Wq + dx1;  dx = dk Wk + dv Wv + LN1'(x, dQ) [out];  LN1 affine partials -> part (as above).
- * WinT = in_proj_weight^T ([d][3d] bf16). */
-int rs_sas_block_in_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
-                        const float* mean1, const float* rstd1, const float* ln_w, const void* WinT, void* dx,
-                        float* part, void* stream);
-/* Block-boundary launches (rowchain.hip): two adjacent row chains of the step in ONE launch, the tensor handed from
- * the first to the second kept in registers.  The argument lists are the unions of the two entries they replace and
- * the results are bitwise those of the two entries called back to back, for every M: the one-launch kernels run
- * where every wave of the grid owns at most one 16-row tile (rs_sas_block_boundary_fused(M, d) == 1: d in {64, 128}
- * and M <= 128 * CUs), the two single-block kernels are launched on the stream otherwise.
- *   rs_sas_block_out_in: rs_sas_block_out of block i (every saved tensor still stored, xn included: it is block
- *     i+1's saved input), then rs_sas_block_in(x = xn) with block i+1's ln1_w/ln1_b/eps1, Wq/bq, Wkv/bkv ->
- *     Qn, mean1, rstd1, q, kv.
- *   rs_sas_block_in_out_bwd: rs_sas_block_in_bwd of block i (LN1 partials -> part1), then
- *     rs_sas_block_out_bwd_delta(dxn = dx) of block i-1 (h1, x1, mean2, rstd2, ln2_w, W*T, outputs dy2, da1, dx1o,
- *     dout, LN2 partials -> part2, optional o/delta).  In the one-launch kernel dx is NOT written; the dx scratch
- *     [M][d] is used only by the two-launch path and may be NULL when rs_sas_block_boundary_fused(M, d) (RS_ERR_ARG
- *     if it is NULL and needed).
- * RS_ERR_UNSUPPORTED for other d. */
-int rs_sas_block_boundary_fused(int64_t M, int64_t d);
-int rs_sas_block_out_in(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo, void* x1,
-                        const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
-                        const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
-                        const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2, const uint64_t* seed_base,
-                        const float* ln1_w, const float* ln1_b, float eps1, void* Qn, float* mean1, float* rstd1,
-                        const void* Wq, const float* bq, void* q, const void* Wkv, const float* bkv, void* kv,
-                        void* stream);
-int rs_sas_block_in_out_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
-                            const float* mean1, const float* rstd1, const float* ln1_w, const void* WinT, void* dx,
-                            float* part1, const int64_t* ids, const void* h1, const void* x1, const float* mean2,
-                            const float* rstd2, const float* ln2_w, const void* W2T, const void* W1T, const void* WoT,
-                            void* dy2, void* da1, void* dx1o, void* dout, float* part2, float drop_p, uint64_t salt1,
-                            uint64_t salt2, const uint64_t* seed_base, const void* o, float* delta, void* stream);
-/* The forward/backward turnaround of the fused training step (rowchain.hip): rs_sas_block_out_head of the LAST block
- * and, on the same rows, that block's rs_sas_block_out_bwd_delta(dxn = dx, h1, x1, mean2 = mean, rstd2 = rstd, ln_w,
- * o) in ONE launch: dx_L, h1, x1, o and the row statistics pass from the forward chain to the backward chain in
- * registers.  Results are bitwise those of the two entries called back to back, for every M: the one-launch kernel
- * runs where rs_sas_block_boundary_fused(M, d), the two kernels are launched on the stream otherwise.  Every output
- * of either entry is written (x1, mean, rstd, xn included) except dx, which the one-launch kernel does NOT write: it
- * is the two-launch path's scratch and may be NULL when rs_sas_block_boundary_fused(M, d) (RS_ERR_ARG if it is NULL
- * and needed).  W2T / W1T / WoT: the block's transposed weights (they must be current when the launch runs);
- * part2: the forward-LN partials (rs_sas_block_out_bwd's part); delta: optional, rowsum(dout * o).
- * Error codes as rs_sas_block_out_head. */
-int rs_sas_block_out_head_bwd(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo,
-                              void* x1, const float* ln_w, const float* ln_b, float eps, void* z, float* mean,
-                              float* rstd, const void* W1, const float* b1, void* h1, const void* W2, const float* b2,
-                              void* xn, const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2,
-                              const uint64_t* seed_base, const void* E, const int64_t* pos, const int64_t* neg,
-                              const float* lnl_w, const float* lnl_b, const int* count_parts, int64_t ncount,
-                              const float* divisor, void* f, float* pl, float* nl, float* dpl, float* dnl, void* dx,
-                              float* lnpart, float* part, const void* W2T, const void* W1T, const void* WoT, void* dy2,
-                              void* da1, void* dx1, void* dout, float* part2, float* delta, void* stream);
 /* Batched bf16 transpose: for m < nmat, desc[6m..6m+5] = {rows, cols, src_off, lds, dst_off, ldd}
  * (elements): dst[dst_off + c*ldd + r] = src[src_off + r*lds + c].  Grid x = max_tiles >= the
  * largest ceil(rows/64)*ceil(cols/64). */
@@ -794,6 +878,19 @@ int rs_uniform_items(const uint64_t* seed_base, uint64_t salt, int64_t item_num,
 
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);
+/* sizeof of the structs of this header that bindings mirror (host only); -1 for an unknown index. */
+enum {
+  RS_SIZEOF_EPILOGUE = 0,
+  RS_SIZEOF_WGRAD_PROBLEM = 1,
+  RS_SIZEOF_REDUCE_SEGMENT = 2,
+  RS_SIZEOF_SAS_EMBED_ARGS = 3,
+  RS_SIZEOF_SAS_IN_ARGS = 4,
+  RS_SIZEOF_SAS_HEAD_ARGS = 5,
+  RS_SIZEOF_SAS_OUT_ARGS = 6,
+  RS_SIZEOF_SAS_OUT_BWD_ARGS = 7,
+  RS_SIZEOF_SAS_IN_BWD_ARGS = 8
+};
+int64_t rs_abi_sizeof(int which);
 
 #ifdef __cplusplus
 }

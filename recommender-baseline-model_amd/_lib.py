@@ -44,6 +44,53 @@ class ReduceSegment(C.Structure):
     _fields_ = [("src", vp), ("stride", i64), ("splits", i64), ("n", i64), ("out", vp)]
 
 
+class SasEmbedArgs(C.Structure):
+    """Mirror of ``rs_sas_embed_args`` (the row-chain kernels' argument structs: fields documented in the header)."""
+    _fields_ = [("ids", vp), ("item_emb", vp), ("pos_emb", vp), ("T", i64), ("scale", f32), ("drop_p", f32),
+                ("salt", u64), ("seed_base", vp), ("x0", vp), ("count_ids", vp), ("count_parts", vp)]
+
+
+class SasInArgs(C.Structure):
+    """Mirror of ``rs_sas_in_args``."""
+    _fields_ = [("M", i64), ("x", vp), ("ldx", i64), ("ln_w", vp), ("ln_b", vp), ("eps", f32), ("Q", vp),
+                ("mean", vp), ("rstd", vp), ("Wq", vp), ("bq", vp), ("q", vp), ("Wkv", vp), ("bkv", vp), ("kv", vp),
+                ("e", SasEmbedArgs)]
+
+
+class SasHeadArgs(C.Structure):
+    """Mirror of ``rs_sas_head_args``."""
+    _fields_ = [("E", vp), ("pos", vp), ("neg", vp), ("ln_w", vp), ("ln_b", vp), ("eps", f32), ("count_parts", vp),
+                ("ncount", i32), ("divisor", vp), ("f", vp), ("pl", vp), ("nl", vp), ("dpl", vp), ("dnl", vp),
+                ("dx", vp), ("lnpart", vp), ("part", vp)]
+
+
+class SasOutArgs(C.Structure):
+    """Mirror of ``rs_sas_out_args``."""
+    _fields_ = [("M", i64), ("o", vp), ("Q", vp), ("Wo", vp), ("bo", vp), ("x1", vp), ("ln_w", vp), ("ln_b", vp),
+                ("eps", f32), ("z", vp), ("mean", vp), ("rstd", vp), ("W1", vp), ("b1", vp), ("h1", vp), ("W2", vp),
+                ("b2", vp), ("xn", vp), ("ids", vp), ("drop_p", f32), ("salt1", u64), ("salt2", u64),
+                ("seed_base", vp), ("h", SasHeadArgs)]
+
+
+class SasOutBwdArgs(C.Structure):
+    """Mirror of ``rs_sas_out_bwd_args``."""
+    _fields_ = [("M", i64), ("dxn", vp), ("ids", vp), ("h1", vp), ("x1", vp), ("mean2", vp), ("rstd2", vp),
+                ("ln_w", vp), ("W2T", vp), ("W1T", vp), ("WoT", vp), ("dy2", vp), ("da1", vp), ("dx1", vp),
+                ("dout", vp), ("part", vp), ("drop_p", f32), ("salt1", u64), ("salt2", u64), ("seed_base", vp),
+                ("o", vp), ("delta", vp)]
+
+
+class SasInBwdArgs(C.Structure):
+    """Mirror of ``rs_sas_in_bwd_args``."""
+    _fields_ = [("M", i64), ("dq", vp), ("dkv", vp), ("dx1", vp), ("x", vp), ("mean1", vp), ("rstd1", vp),
+                ("ln_w", vp), ("WinT", vp), ("ldwt", i64), ("dx", vp), ("part", vp)]
+
+
+# header struct name -> mirror, in the order of rs_abi_sizeof's indices (RS_SIZEOF_*)
+STRUCTS = {"rs_epilogue": Epilogue, "rs_wgrad_problem": WgradProblem, "rs_reduce_segment": ReduceSegment,
+           "rs_sas_embed_args": SasEmbedArgs, "rs_sas_in_args": SasInArgs, "rs_sas_head_args": SasHeadArgs,
+           "rs_sas_out_args": SasOutArgs, "rs_sas_out_bwd_args": SasOutBwdArgs, "rs_sas_in_bwd_args": SasInBwdArgs}
+
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_BWD, ACT_GELU_BWD = 0, 1, 2, 3, 4
 
 # name -> argtypes (all return int)
@@ -100,33 +147,21 @@ SIGNATURES = {
     "rs_vocab_shard_label_logits": [i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, vp],
     "rs_vocab_shard_combine": [i32, i64, vp, vp, vp, vp, vp, vp],
     "rs_seed_advance": [vp, vp],
-    "rs_sas_block_parts": [i64],
     "rs_touched_rows_ws_numel": [i64],
     "rs_touched_rows": [vp, i64, i64, vp, vp, vp, vp, vp],
     "rs_rows_pack": [vp, i64, i64, vp, vp, vp, i64, vp],
     "rs_rows_unpack": [vp, i64, i64, vp, vp, vp],
-    "rs_sas_block_in": [i64, i64, vp, i64, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "rs_sas_block_in_count_parts": [i64],
     "rs_sas_block_grid": [i64],
-    "rs_sas_block_out_head": [i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32,
-                              u64, u64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "rs_sas_block_in_embed": [i64, i64, vp, i64, vp, vp, f32, f32, u64, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp,
-                              vp, vp, vp, vp, vp, vp],
-    "rs_sas_block_out": [i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32,
-                         u64, u64, vp, vp],
+    "rs_sas_block_boundary_fused": [i64, i64],
+    "rs_sas_block_in": [i64, C.POINTER(SasInArgs), vp],
+    "rs_sas_block_out": [i64, C.POINTER(SasOutArgs), vp],
+    "rs_sas_block_out_bwd_delta": [i64, C.POINTER(SasOutBwdArgs), vp],
     "rs_sas_block_out_bwd": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, u64, u64,
                              vp, vp],
-    "rs_sas_block_out_bwd_delta": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, u64,
-                                   u64, vp, vp, vp, vp],
-    "rs_sas_block_in_bwd": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "rs_sas_block_boundary_fused": [i64, i64],
-    "rs_sas_block_out_in": [i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32,
-                            u64, u64, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "rs_sas_block_in_out_bwd": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                vp, vp, vp, vp, vp, f32, u64, u64, vp, vp, vp, vp],
-    "rs_sas_block_out_head_bwd": [i64, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                  f32, u64, u64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "rs_sas_block_in_bwd": [i64, C.POINTER(SasInBwdArgs), vp],
+    "rs_sas_block_out_in": [i64, C.POINTER(SasOutArgs), C.POINTER(SasInArgs), vp],
+    "rs_sas_block_in_out_bwd": [i64, C.POINTER(SasInBwdArgs), C.POINTER(SasOutBwdArgs), vp],
+    "rs_sas_block_out_head_bwd": [i64, C.POINTER(SasOutArgs), C.POINTER(SasOutBwdArgs), vp],
     "rs_wgrad_grouped": [i32, C.POINTER(WgradProblem), i64, i64, vp, i64, i32, C.POINTER(ReduceSegment), vp],
     "rs_reduce_segments": [i32, C.POINTER(ReduceSegment), i32, vp],
     "rs_wgrad_grouped_slab_numel": [i32, C.POINTER(WgradProblem), i64, i64],
@@ -173,12 +208,12 @@ SIGNATURES = {
     "rs_attn_bwd_plan": [i64, i64, i64, i32, vp, C.POINTER(i32)],
     "rs_attn_lds_regime": [i32, i64, i64, i64, i64, i32, C.POINTER(i32)],
     "rs_abi_version": [],
+    "rs_abi_sizeof": [i32],
 }
 
-RESTYPES = {"rs_wgrad_grouped_slab_numel": C.c_int64, "rs_sas_block_parts": C.c_int64,
+RESTYPES = {"rs_wgrad_grouped_slab_numel": C.c_int64, "rs_abi_sizeof": C.c_int64,
             "rs_touched_rows_ws_numel": C.c_int64, "rs_item_index_ws_bytes": C.c_int64,
             "rs_vocab_ce_ws_numel": C.c_int64, "rs_full_ws_bytes": C.c_int64,
-            "rs_sas_block_in_count_parts": C.c_int64,
             "rs_sas_block_grid": C.c_int64, "rs_layernorm_bwd_nparts": C.c_int64,
             "rs_sas_ce_rows_nparts": C.c_int64, "rs_sas_sce_max_k": C.c_int64,
             "rs_sas_sce_ws_bytes": C.c_int64, "rs_sas_sce_dh_splits": C.c_int64}

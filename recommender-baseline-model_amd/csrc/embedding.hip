@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
     const float keep = (mode == 0 && id == 0) ? 0.f : 1.f;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      // one rounding (fma), spelled out: rs_sas_block_in_embed (rowchain.hip embed_tile) forms the same value, and
+      // one rounding (fma), spelled out: rs_sas_block_in's embed form (rowchain.hip embed_tile) forms the same value, and
       // left to the compiler the select between the two modes kept this one a separate multiply and add
       float x = mode == 0 ? __builtin_fmaf(e[j], scale, p[j]) : e[j] + p[j];
       if (drop_p > 0.f) x *= drop_mul(drop_p, seed, (uint64_t)(r * d + c + j));

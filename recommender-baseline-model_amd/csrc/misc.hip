@@ -630,6 +630,21 @@ int rs_wall_clock_khz(int* khz) {
   return (int)hipDeviceGetAttribute(khz, hipDeviceAttributeWallClockRate, dev);
 }
 
-int rs_abi_version(void) { return 1; }
+int rs_abi_version(void) { return 2; }
+
+int64_t rs_abi_sizeof(int which) {
+  switch (which) {
+    case RS_SIZEOF_EPILOGUE: return sizeof(rs_epilogue);
+    case RS_SIZEOF_WGRAD_PROBLEM: return sizeof(rs_wgrad_problem);
+    case RS_SIZEOF_REDUCE_SEGMENT: return sizeof(rs_reduce_segment);
+    case RS_SIZEOF_SAS_EMBED_ARGS: return sizeof(rs_sas_embed_args);
+    case RS_SIZEOF_SAS_IN_ARGS: return sizeof(rs_sas_in_args);
+    case RS_SIZEOF_SAS_HEAD_ARGS: return sizeof(rs_sas_head_args);
+    case RS_SIZEOF_SAS_OUT_ARGS: return sizeof(rs_sas_out_args);
+    case RS_SIZEOF_SAS_OUT_BWD_ARGS: return sizeof(rs_sas_out_bwd_args);
+    case RS_SIZEOF_SAS_IN_BWD_ARGS: return sizeof(rs_sas_in_bwd_args);
+    default: return -1;
+  }
+}
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // Wave-resident row chains for the SASRec sublayers (bf16, gfx950): the kernels behind
-// rs_sas_block_in / rs_sas_block_out / rs_sas_block_out_bwd / rs_sas_block_in_bwd.
+// rs_sas_block_in / rs_sas_block_out / rs_sas_block_out_bwd / rs_sas_block_in_bwd and the two-chain entries
+// rs_sas_block_out_in / rs_sas_block_in_out_bwd / rs_sas_block_out_head_bwd.  Their arguments are the public structs
+// of recsys_hip.h, taken by the kernels as they are.
 //
 // Everything in a SAS block except the attention core is row-local (BS/models/sas_model/sas.py:73-76 before the
 // core: Q = LN1(x), q = Q Wq^T + bq, kv = x Wkv^T + bkv; sas.py:75-84 after it: x1 = Q + O Wo^T + bo, z = LN2(x1),
@@ -22,7 +24,7 @@
 //    statistics are 2 cross-group shuffles;
 //  * global loads/stores of activations use the same layout (8 bytes per lane per 16
 //    features), LayerNorm affine partials accumulate per lane over the wave's tiles and are
-//    reduced once per workgroup (partial set = workgroup: rs_sas_block_parts sets).
+//    reduced once per workgroup (partial set = workgroup: rs_sas_block_grid sets).
 #include "common.h"
 #include "../../include/recsys_hip.h"
 
@@ -39,10 +41,6 @@ __device__ unsigned long long g_rc_prof[4096 * 8 * 16];
 #define RCPROF(slot) \
   do {               \
   } while (0)
-#endif
-
-#ifndef RC_HEAD_PREFETCH
-#define RC_HEAD_PREFETCH 1   // head item-row loads: 0 tile start, 1 mid-chain (A/B 0.2999 vs 0.3020 ms at cfg2), 2 after the chain, 3 ids at the start + rows mid-chain (18 VGPRs spilled: 0.2975 vs 0.2953)
 #endif
 
 #ifndef RC_NOSTORE
@@ -617,30 +615,16 @@ __device__ __forceinline__ void bwd_out_b(const Raw<D>& dar, const Raw<D>& xr, c
 }
 
 // ------------------------------------------------------------------ single-block kernels
-// The SAS embedding stage folded into the first block's input kernel (rs_sas_block_in_embed): the tile's
+// The SAS embedding stage folded into the first block's input kernel (rs_sas_in_args.e): the tile's
 // x = (item_emb[ids]·scale + pos_emb[t]) → dropout → ·(ids != 0) is formed in registers exactly as
 // embed_fwd_kernel forms it (same expression, same hash index r·d + c), stored (x0, the backward's LN1 input) and
 // fed to the chain; each workgroup also counts its tiles' valid positions (count_ids != 0) into
 // count_parts[workgroup] (the head kernel's 256 workgroups then load one word per thread, not a dependent chain of 8).
-struct EmbIn {
-  const int64_t* ids; const bf16* etab; const bf16* ptab; int64_t T;
-  float scale, drop_p; uint64_t salt; const uint64_t* seed_base;
-  bf16* xout; const int64_t* cnt_ids; int* cnt_parts;
-};
-struct InArgs {
-  int64_t M;
-  const bf16* x; int64_t ldx;
-  const float* ln_w; const float* ln_b; float eps;
-  bf16* Q; float* mean; float* rstd;
-  const bf16* Wq; const float* bq; bf16* q;
-  const bf16* Wkv; const float* bkv; bf16* kv;
-  EmbIn e;                                                  // e.etab == nullptr: x is read
-};
 template <int D>
-__device__ __forceinline__ void embed_tile(Raw<D>& xr, const EmbIn& e, const Tile& T, uint32_t s32, int g) {
+__device__ __forceinline__ void embed_tile(Raw<D>& xr, const rs_sas_embed_args& e, const Tile& T, uint32_t s32, int g) {
   const int64_t id = e.ids[T.mc], t = T.mc % e.T;
-  const bf16* ep = e.etab + id * D + 8 * g;
-  const bf16* pp = e.ptab + t * D + 8 * g;
+  const bf16* ep = e.item_emb + id * D + 8 * g;
+  const bf16* pp = e.pos_emb + t * D + 8 * g;
   bf16x8 ev[Lay<D>::S], pv[Lay<D>::S];
 #pragma unroll
   for (int s = 0; s < Lay<D>::S; ++s) {
@@ -667,7 +651,7 @@ __device__ __forceinline__ void embed_tile(Raw<D>& xr, const EmbIn& e, const Til
 
 // X -> Q = LN1(X) [saved], q = Q Wq^T + bq, kv = X Wkv^T + bkv
 template <int D>
-__global__ __launch_bounds__(NT) void block_in_kernel(InArgs a) {
+__global__ __launch_bounds__(NT) void block_in_kernel(rs_sas_in_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef Smem<D, 3, 5, 0> L;
   constexpr int WB = Lay<D>::WBYTES;
@@ -676,7 +660,7 @@ __global__ __launch_bounds__(NT) void block_in_kernel(InArgs a) {
             cl = lane & 15;
   const TileRange tr = tiles_of_wave(n_tiles(a.M), wave);
   int64_t t = tr.first;
-  const bool emb = a.e.etab != nullptr;
+  const bool emb = a.e.item_emb != nullptr;
   const uint32_t es32 = emb && a.e.drop_p > 0.f ? seed32(eff_seed(a.e.salt, a.e.seed_base)) : 0u;
   int cnt = 0;
   auto load_x = [&](Raw<D>& xr, const Tile& T) {
@@ -686,10 +670,10 @@ __global__ __launch_bounds__(NT) void block_in_kernel(InArgs a) {
     }
     // the count's id load goes out with the gathers and is consumed before the x0 store: vmcnt retires in order
     // and counts stores too on gfx950, so a load consumed after a store waits for that store
-    const int64_t cid = a.e.cnt_ids && T.ok && g == 0 ? a.e.cnt_ids[T.mc] : 0;
+    const int64_t cid = a.e.count_ids && T.ok && g == 0 ? a.e.count_ids[T.mc] : 0;
     embed_tile<D>(xr, a.e, T, es32, g);
-    if (a.e.cnt_ids) cnt += __popcll(__ballot(cid != 0));
-    store_raw<D>(a.e.xout, D, T.m, T.ok, xr, g);
+    if (a.e.count_ids) cnt += __popcll(__ballot(cid != 0));
+    store_raw<D>(a.e.x0, D, T.m, T.ok, xr, g);
   };
   Raw<D> xr;
   if (t < tr.end) load_x(xr, tile_of(t, a.M, cl));
@@ -708,7 +692,7 @@ __global__ __launch_bounds__(NT) void block_in_kernel(InArgs a) {
     fwd_in_q<D>(xr, T, wslot(smem, 0, WB), lv, a.eps, a.Q, a.mean, a.rstd, a.q, lane);
     fwd_in_kv<D>(xr, T, wslot(smem, 1, WB), wslot(smem, 2, WB), lv, a.kv, lane);
   }
-  if (emb && a.e.cnt_parts) {   // integer counts: exact in any order
+  if (emb && a.e.count_parts) {   // integer counts: exact in any order
     __shared__ int wcnt[NW];
     if (lane == 0) wcnt[wave] = cnt;
     __syncthreads();
@@ -716,56 +700,35 @@ __global__ __launch_bounds__(NT) void block_in_kernel(InArgs a) {
       int c = 0;
 #pragma unroll
       for (int w = 0; w < NW; ++w) c += wcnt[w];
-      a.e.cnt_parts[blockIdx.x] = c;
+      a.e.count_parts[blockIdx.x] = c;
     }
   }
 }
 
-// The SAS output head riding in the LAST block's output kernel (rs_sas_block_out_head): every quantity of the head
+// The SAS output head riding in the LAST block's output kernel (rs_sas_out_args.h): every quantity of the head
 // is token-local once the BCE divisor is known (the valid-position count, summed from the first block's per-wave
 // counts), so each tile's x_L = x' goes on, in registers, through the last LayerNorm (f saved), the tied sampled
 // logits <f, E[pos]>, <f, E[neg]>, the BCE gradient (dpl, dnl saved), df = dpl E[pos] + dnl E[neg] and the last
 // LayerNorm's backward (dx_L saved for the blocks' backward; affine partials per workgroup, BCE partials sp, sn,
 // count per workgroup for the loss statistics).  Same math as head.hip's kernels (sums in this layout's order).
-struct HeadArgs {
-  const bf16* E; const int64_t* pos; const int64_t* neg;
-  const float* gl; const float* bl; float eps;
-  const int* cnt_parts; int ncnt; const float* divisor;
-  bf16* f; float* pl; float* nl; float* dpl; float* dnl; bf16* dx; float* lnpart; float* part;
-};
-struct OutArgs {
-  int64_t M;
-  const bf16* o; const bf16* Q;
-  const bf16* Wo; const float* bo; bf16* x1;
-  const float* ln_w; const float* ln_b; float eps; bf16* z; float* mean; float* rstd;
-  const bf16* W1; const float* b1; bf16* h1;
-  const bf16* W2; const float* b2; bf16* xn;
-  const int64_t* ids;
-  float drop_p; uint64_t salt1, salt2; const uint64_t* seed_base;
-  HeadArgs h;                                               // h.E == nullptr: no head
-};
 __device__ __forceinline__ float h_softplus(float z) { return fmaxf(z, 0.f) + log1pf(__expf(-fabsf(z))); }
 __device__ __forceinline__ float h_sigmoid(float z) { return 1.f / (1.f + __expf(-z)); }
 
-// the tile's item rows E[pos], E[neg] (issued at the tile's start: their latency hides behind the block's chain)
+// the tile's item rows E[pos], E[neg].  block_out_kernel requests them mid-chain, between fwd_out_a and fwd_out_b
+// (cfg2 A/B, ms per launch: 0.2999 against 0.3020 at the tile's start; the ids at the start and the rows mid-chain
+// spilled 18 VGPRs: 0.2975 against 0.2953 for mid-chain in that session)
 template <int D>
-__device__ __forceinline__ int64_t head_rows(const HeadArgs& h, const Tile& T, Raw<D>& er, Raw<D>& nr, int g) {
+__device__ __forceinline__ int64_t head_rows(const rs_sas_head_args& h, const Tile& T, Raw<D>& er, Raw<D>& nr, int g) {
   const int64_t ip = h.pos[T.mc], in = h.neg[T.mc];
   load_raw<D>(er, h.E, D, ip, g);
   load_raw<D>(nr, h.E, D, in, g);
   return ip;
 }
-template <int D>
-__device__ __forceinline__ void head_rows_at(const HeadArgs& h, int64_t ip, int64_t in, Raw<D>& er, Raw<D>& nr,
-                                             int g) {
-  load_raw<D>(er, h.E, D, ip, g);
-  load_raw<D>(nr, h.E, D, in, g);
-}
 // (head_tile_x hands dx_L back, rounded as stored; STORE_DX false: the turnaround kernel -- dx_L in registers only,
 // and the LayerNorm in the form that does not depend on the kernel around it, ln_fwd_head)
 template <int D, bool STORE_DX>
 __device__ __forceinline__ void head_tile_x(const Raw<D>& xr, const Raw<D>& er, const Raw<D>& nr, int64_t ip,
-                                            const Tile& T, const float* gl, const float* bl, const HeadArgs& h,
+                                            const Tile& T, const float* gl, const float* bl, const rs_sas_head_args& h,
                                             float scale, float* red, float (&acc)[3], int lane, int wave,
                                             Raw<D>& dxr) {
   const int g = lane >> 4;
@@ -815,12 +778,12 @@ __device__ __forceinline__ void head_tile_x(const Raw<D>& xr, const Raw<D>& er, 
 }
 template <int D>
 __device__ __forceinline__ void head_tile(const Raw<D>& xr, const Raw<D>& er, const Raw<D>& nr, int64_t ip,
-                                          const Tile& T, const float* gl, const float* bl, const HeadArgs& h,
+                                          const Tile& T, const float* gl, const float* bl, const rs_sas_head_args& h,
                                           float scale, float* red, float (&acc)[3], int lane, int wave) {
   Raw<D> dr;
   head_tile_x<D, true>(xr, er, nr, ip, T, gl, bl, h, scale, red, acc, lane, wave, dr);
 }
-__device__ __forceinline__ OutFwd out_fwd_of(const OutArgs& a) {
+__device__ __forceinline__ OutFwd out_fwd_of(const rs_sas_out_args& a) {
   const bool drop = a.drop_p > 0.f;
   return OutFwd{a.x1, a.z, a.h1, a.xn, a.mean, a.rstd, a.ids, a.drop_p, a.eps,
                 drop ? seed32(eff_seed(a.salt1, a.seed_base)) : 0u, drop ? seed32(eff_seed(a.salt2, a.seed_base)) : 0u};
@@ -829,7 +792,7 @@ __device__ __forceinline__ OutFwd out_fwd_of(const OutArgs& a) {
 // O -> x1 = Q + O Wo^T + bo [saved], z = LN2(x1) [saved], h1 = relu(drop(z W1^T + b1)) [saved],
 // x' = (drop(h1 W2^T + b2) + z) * (ids != 0)
 template <int D, bool HEAD>
-__global__ __launch_bounds__(NT) void block_out_kernel(OutArgs a) {
+__global__ __launch_bounds__(NT) void block_out_kernel(rs_sas_out_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef Smem<D, 3, 7, 1> L;
   constexpr int WB = Lay<D>::WBYTES;
@@ -854,7 +817,7 @@ __global__ __launch_bounds__(NT) void block_out_kernel(OutArgs a) {
     const int64_t ldw[3] = {D, D, D};
     stage_w<D, 3>(smem, W, ldw, wave, lane);
     if (head) {
-      const float* const V[7] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2, a.h.gl, a.h.bl};
+      const float* const V[7] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2, a.h.ln_w, a.h.ln_b};
       stage_v<D, 7>(reinterpret_cast<float*>(smem + L::W), V, tid);
     } else {
       const float* const V[5] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2};
@@ -867,7 +830,7 @@ __global__ __launch_bounds__(NT) void block_out_kernel(OutArgs a) {
   if (head) {
     ln_zero(red, D, lane, wave);
     int c = 0;
-    for (int i = tid; i < a.h.ncnt; i += NT) c += a.h.cnt_parts[i];
+    for (int i = tid; i < a.h.ncount; i += NT) c += a.h.count_parts[i];
     c = (int)wave_sum((float)c);   // exact: counts < 2^24
     if (lane == 0) hred[3][wave] = (float)c;
   }
@@ -887,21 +850,12 @@ __global__ __launch_bounds__(NT) void block_out_kernel(OutArgs a) {
       load_raw<D>(Qr, a.Q, D, T.mc, g);
     }
     Raw<D> zr, hr, xr, er, nr;
-    int64_t ip = 0, in = 0;
-    if (head && RC_HEAD_PREFETCH == 0) ip = head_rows<D>(a.h, T, er, nr, g);
-    // 3: the tile's item ids at its start (before any store: vmcnt retires in order and counts stores, so an
-    // index load issued after the chain's stores would wait for them), the item rows mid-chain
-    if (head && RC_HEAD_PREFETCH == 3) {
-      ip = a.h.pos[T.mc];
-      in = a.h.neg[T.mc];
-    }
+    int64_t ip = 0;
     fwd_out_a<D>(orr, Qr, T, wslot(smem, 0, WB), wslot(smem, 1, WB), lv, of, zr, hr, lane);
     RCPROF(2);
-    if (head && RC_HEAD_PREFETCH == 1) ip = head_rows<D>(a.h, T, er, nr, g);
-    if (head && RC_HEAD_PREFETCH == 3) head_rows_at<D>(a.h, ip, in, er, nr, g);
+    if (head) ip = head_rows<D>(a.h, T, er, nr, g);
     fwd_out_b<D>(hr, zr, T, wslot(smem, 2, WB), lv, of, xr, lane);
     RCPROF(4);
-    if (head && RC_HEAD_PREFETCH == 2) ip = head_rows<D>(a.h, T, er, nr, g);
     if (head) head_tile<D>(xr, er, nr, ip, T, lv + 5 * D, lv + 6 * D, a.h, hscale, red, hacc, lane, wave);
     RCPROF(6);
   }
@@ -923,16 +877,7 @@ __global__ __launch_bounds__(NT) void block_out_kernel(OutArgs a) {
   }
 }
 
-struct OutBwdArgs {
-  int64_t M;
-  const bf16* dxn; const int64_t* ids;
-  const bf16* h1; const bf16* x1; const float* mean2; const float* rstd2; const float* ln_w;
-  const bf16* W2T; const bf16* W1T; const bf16* WoT;      // transposed [in][out] copies
-  bf16* dy2; bf16* da1; bf16* dx1; bf16* dout; float* part;
-  float drop_p; uint64_t salt1, salt2; const uint64_t* seed_base;
-  const bf16* o; float* delta;                              // optional (both or neither)
-};
-__device__ __forceinline__ OutBwd out_bwd_of(const OutBwdArgs& a) {
+__device__ __forceinline__ OutBwd out_bwd_of(const rs_sas_out_bwd_args& a) {
   const bool drop = a.drop_p > 0.f;
   return OutBwd{a.dy2, a.da1, a.dx1, a.dout, a.delta, a.ids, a.drop_p,
                 drop ? seed32(eff_seed(a.salt1, a.seed_base)) : 0u, drop ? seed32(eff_seed(a.salt2, a.seed_base)) : 0u};
@@ -941,7 +886,7 @@ __device__ __forceinline__ OutBwd out_bwd_of(const OutBwdArgs& a) {
 // dzres = dxn*mask; dy2 = drop2(dzres) [saved]; da1 = relu'(h1)*drop1(dy2 W2) [saved]; dz = da1 W1 + dzres;
 // dx1 = LN2'(x1, dz) [saved, + affine partials]; dout = dx1 Wo
 template <int D>
-__global__ __launch_bounds__(NT) void block_out_bwd_kernel(OutBwdArgs a) {
+__global__ __launch_bounds__(NT) void block_out_bwd_kernel(rs_sas_out_bwd_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef Smem<D, 3, 1, 1> L;
   constexpr int WB = Lay<D>::WBYTES;
@@ -985,17 +930,9 @@ __global__ __launch_bounds__(NT) void block_out_bwd_kernel(OutBwdArgs a) {
   ln_partials<D>(red, a.part, tid);
 }
 
-struct InBwdArgs {
-  int64_t M;
-  const bf16* dq; const bf16* dkv; const bf16* dx1; const bf16* x;
-  const float* mean1; const float* rstd1; const float* ln_w;
-  const bf16* WinT; int64_t ldwt;                       // in_proj^T [d][3d]
-  bf16* dx; float* part;
-};
-
 // dx_kv = dk Wk + dv Wv; dQ = dq Wq + dx1; dx = dx_kv + LN1'(x, dQ) (+ affine partials)
 template <int D>
-__global__ __launch_bounds__(NT) void block_in_bwd_kernel(InBwdArgs a) {
+__global__ __launch_bounds__(NT) void block_in_bwd_kernel(rs_sas_in_bwd_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef Smem<D, 3, 1, 1> L;
   constexpr int WB = Lay<D>::WBYTES;
@@ -1091,7 +1028,7 @@ __device__ __forceinline__ void as_loaded(Raw<D>& r) {
 
 // o (block i) -> block_out_kernel<D, false>'s chain -> xn [saved] -> block_in_kernel's chain with block i+1's weights
 template <int D>
-__global__ __launch_bounds__(NT) void block_out_in_kernel(OutArgs a, InArgs b) {
+__global__ __launch_bounds__(NT) void block_out_in_kernel(rs_sas_out_args a, rs_sas_in_args b) {
   typedef Roll<D> R;
   RC_BOUNDARY_SLOTS(D);
   __shared__ __attribute__((aligned(16))) float lv[10 * D];   // bo, ln2_w, ln2_b, b1, b2 | ln1_w, ln1_b, bq, bk, bv
@@ -1146,7 +1083,7 @@ __global__ __launch_bounds__(NT) void block_out_in_kernel(OutArgs a, InArgs b) {
 // block i's block_in_bwd_kernel chain -> dx (registers only: never stored) -> block i-1's block_out_bwd_kernel chain.
 // red: block i's attention-LN partials, then block i-1's forward-LN partials (per workgroup, as the single kernels)
 template <int D>
-__global__ __launch_bounds__(NT) void block_in_out_bwd_kernel(InBwdArgs a, OutBwdArgs b) {
+__global__ __launch_bounds__(NT) void block_in_out_bwd_kernel(rs_sas_in_bwd_args a, rs_sas_out_bwd_args b) {
   typedef Roll<D> R;
   RC_BOUNDARY_SLOTS(D);
   __shared__ __attribute__((aligned(16))) float lv[2 * D];   // ln1_w (block i) | ln2_w (block i-1)
@@ -1236,8 +1173,8 @@ __global__ __launch_bounds__(NT) void block_in_out_bwd_kernel(InBwdArgs a, OutBw
 // from the kernel-argument segment where they are first needed, through a pointer the optimizer cannot see through.
 // Of b only those and W2T are read: the rest (rows, ids, seeds, the saved tensors) are a's.
 struct TurnArgs {
-  OutArgs a;
-  OutBwdArgs b;
+  rs_sas_out_args a;
+  rs_sas_out_bwd_args b;
 };
 typedef const __attribute__((address_space(4))) TurnArgs* TurnArgsPtr;
 __device__ __forceinline__ TurnArgsPtr turn_args_late() {
@@ -1247,7 +1184,7 @@ __device__ __forceinline__ TurnArgsPtr turn_args_late() {
 }
 template <int D>
 __global__ __launch_bounds__(NT) void block_out_head_bwd_kernel(TurnArgs k) {
-  const OutArgs& a = k.a;
+  const rs_sas_out_args& a = k.a;
   typedef Roll<D> R;
   RC_BOUNDARY_SLOTS(D);
   __shared__ __attribute__((aligned(16))) float lv[7 * D];   // bo, ln2_w, ln2_b, b1, b2 | gl, bl
@@ -1280,7 +1217,7 @@ __global__ __launch_bounds__(NT) void block_out_head_bwd_kernel(TurnArgs k) {
     stage_slot<D>(w5, k.b.WoT, D, wave, lane);
   }
   {
-    const float* const V[7] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2, a.h.gl, a.h.bl};
+    const float* const V[7] = {a.bo, a.ln_w, a.ln_b, a.b1, a.b2, a.h.ln_w, a.h.ln_b};
     stage_v<D, 7>(lv, V, tid);
   }
   ln_zero(red, D, lane, wave);
@@ -1289,7 +1226,7 @@ __global__ __launch_bounds__(NT) void block_out_head_bwd_kernel(TurnArgs k) {
   float hacc[3] = {0.f, 0.f, 0.f};
   {
     int c = 0;
-    for (int i = tid; i < a.h.ncnt; i += NT) c += a.h.cnt_parts[i];
+    for (int i = tid; i < a.h.ncount; i += NT) c += a.h.count_parts[i];
     c = (int)wave_sum((float)c);   // exact: counts < 2^24
     if (lane == 0) hred[3][wave] = (float)c;
   }
@@ -1307,7 +1244,8 @@ __global__ __launch_bounds__(NT) void block_out_head_bwd_kernel(TurnArgs k) {
   float mu2 = 0.f, rs2 = 0.f;
   if (has) {
     fwd_out_a_x<D>(orr, Qr, T, wimg(w0), wimg(w1), lv, of, zr, hr, lane, x1r, mu2, rs2);
-    head_rows_at<D>(a.h, ip, in, er, nr, g);   // ahead of the re-stage; they land under fwd_out_b
+    load_raw<D>(er, a.h.E, D, ip, g);   // the item rows, ahead of the re-stage; they land under fwd_out_b
+    load_raw<D>(nr, a.h.E, D, in, g);
   }
   RCPROF(2);
   if constexpr (R::ON) {
@@ -1371,47 +1309,55 @@ static int64_t grid_for(int64_t M) {
   const int64_t nt = (M + TR - 1) / TR;
   return nt < g_ncu ? nt : g_ncu;
 }
-template <int D> static size_t lds_fwd() { return Smem<D, 3, 5, 0>::BYTES; }
-template <int D, bool HEAD> static size_t lds_out() {
-  return HEAD ? Smem<D, 3, 7, 1>::BYTES : Smem<D, 3, 5, 0>::BYTES;
-}
-template <int D> static size_t lds_bwd() { return Smem<D, 3, 1, 1>::BYTES; }
-
-template <typename K>
-static void set_lds(K kern, size_t bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-template <int D, bool HEAD>
-static void launch_out_t(const OutArgs& a, hipStream_t s) {
-  constexpr auto k = block_out_kernel<D, HEAD>;
-  const size_t lds = lds_out<D, HEAD>();
-  set_lds(k, lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid_for(a.M)), dim3(NT), lds, s, a);
-}
-static int launch_out(const OutArgs& a, int64_t d, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const bool head = a.h.E != nullptr;
-  if (d == 64) head ? launch_out_t<64, true>(a, s) : launch_out_t<64, false>(a, s);
-  else if (d == 128) head ? launch_out_t<128, true>(a, s) : launch_out_t<128, false>(a, s);
-  else return RS_ERR_UNSUPPORTED;
-  return (int)hipGetLastError();
-}
-
+static bool width_ok(int64_t d) { return d == 64 || d == 128; }
 // the boundary kernels' precondition: every wave of the grid owns at most one tile
 static bool boundary_fused(int64_t M, int64_t d) {
-  return M > 0 && (d == 64 || d == 128) && (M + TR - 1) / TR <= grid_for(M) * NW;
+  return M > 0 && width_ok(d) && (M + TR - 1) / TR <= grid_for(M) * NW;
+}
+
+// One launcher per kernel: the <64> or <128> instance by d (checked by the entry), grid_for(M) workgroups, the
+// argument structs copied by value into the launch; lds > 0: dynamic LDS (raised above the 64 KB default first).
+// The order of the launchers is the order in which the compiler emits the kernels, and the code it generates for
+// block_in_kernel changed (registers, scheduling) when that kernel was emitted before block_out_kernel: keep it.
+template <typename K, typename... A>
+static int launch(K kern, size_t lds, int64_t M, void* stream, const A&... a) {
+  const void* fn = reinterpret_cast<const void*>(kern);
+  if (lds) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid_for(M)), dim3(NT), lds, (hipStream_t)stream, a...);
+  return (int)hipGetLastError();
 }
 template <int D>
-static void launch_out_in_t(const OutArgs& a, const InArgs& b, hipStream_t s) {
-  hipLaunchKernelGGL(block_out_in_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, a, b);   // static LDS
+static int launch_out_t(const rs_sas_out_args& a, void* s) {
+  return a.h.E ? launch(block_out_kernel<D, true>, Smem<D, 3, 7, 1>::BYTES, a.M, s, a)
+               : launch(block_out_kernel<D, false>, Smem<D, 3, 5, 0>::BYTES, a.M, s, a);
 }
-template <int D>
-static void launch_in_out_bwd_t(const InBwdArgs& a, const OutBwdArgs& b, hipStream_t s) {
-  hipLaunchKernelGGL(block_in_out_bwd_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, a, b);
+static int launch_out(const rs_sas_out_args& a, int64_t d, void* s) {
+  return d == 64 ? launch_out_t<64>(a, s) : launch_out_t<128>(a, s);
 }
-template <int D>
-static void launch_out_head_bwd_t(const OutArgs& a, const OutBwdArgs& b, hipStream_t s) {
-  hipLaunchKernelGGL(block_out_head_bwd_kernel<D>, dim3((unsigned)grid_for(a.M)), dim3(NT), 0, s, TurnArgs{a, b});
+static int launch_in(const rs_sas_in_args& a, int64_t d, void* s) {
+  return d == 64 ? launch(block_in_kernel<64>, Smem<64, 3, 5, 0>::BYTES, a.M, s, a)
+                 : launch(block_in_kernel<128>, Smem<128, 3, 5, 0>::BYTES, a.M, s, a);
+}
+static int launch_out_bwd(const rs_sas_out_bwd_args& a, int64_t d, void* s) {
+  return d == 64 ? launch(block_out_bwd_kernel<64>, Smem<64, 3, 1, 1>::BYTES, a.M, s, a)
+                 : launch(block_out_bwd_kernel<128>, Smem<128, 3, 1, 1>::BYTES, a.M, s, a);
+}
+static int launch_in_bwd(const rs_sas_in_bwd_args& a, int64_t d, void* s) {
+  return d == 64 ? launch(block_in_bwd_kernel<64>, Smem<64, 3, 1, 1>::BYTES, a.M, s, a)
+                 : launch(block_in_bwd_kernel<128>, Smem<128, 3, 1, 1>::BYTES, a.M, s, a);
+}
+// the boundary and turnaround kernels: static LDS
+static int launch_out_in(const rs_sas_out_args& a, const rs_sas_in_args& b, int64_t d, void* s) {
+  return d == 64 ? launch(block_out_in_kernel<64>, 0, a.M, s, a, b) : launch(block_out_in_kernel<128>, 0, a.M, s, a, b);
+}
+static int launch_in_out_bwd(const rs_sas_in_bwd_args& a, const rs_sas_out_bwd_args& b, int64_t d, void* s) {
+  return d == 64 ? launch(block_in_out_bwd_kernel<64>, 0, a.M, s, a, b)
+                 : launch(block_in_out_bwd_kernel<128>, 0, a.M, s, a, b);
+}
+static int launch_out_head_bwd(const rs_sas_out_args& a, const rs_sas_out_bwd_args& b, int64_t d, void* s) {
+  const TurnArgs k = {a, b};
+  return d == 64 ? launch(block_out_head_bwd_kernel<64>, 0, a.M, s, k)
+                 : launch(block_out_head_bwd_kernel<128>, 0, a.M, s, k);
 }
 
 // ------------------------------------------------------------------ batched bf16 transpose
@@ -1441,231 +1387,137 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const int64_t* __re
   }
 }
 
+// ------------------------------------------------------------------ entry points
+// Every entry checks its arguments before its first HIP call (the *_ok functions below: plain host code), then
+// copies the caller's structs, fills the fields the header marks "set by the entry" in the copies and hands them to
+// the launch by value: nothing refers to the caller's structs once the entry has returned.
+static bool aligned16(const void* a, const void* b, const void* c) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+// x_given: the caller's x / ldx are used (else the entry sets them)
+static bool in_ok(const rs_sas_in_args* a, bool x_given) {
+  if (!a || a->M <= 0) return false;
+  const rs_sas_embed_args& e = a->e;
+  if (!e.item_emb) return !x_given || a->ldx % 8 == 0;
+  return e.T > 0 && a->M % e.T == 0 && e.ids && e.pos_emb && e.x0 && !e.count_ids == !e.count_parts &&
+         aligned16(e.item_emb, e.pos_emb, e.x0);
+}
+// dx_needed: the head's dx is written (else it is a scratch that may be absent)
+static bool out_ok(const rs_sas_out_args* a, bool dx_needed) {
+  if (!a || a->M <= 0) return false;
+  const rs_sas_head_args& h = a->h;
+  if (!h.E) return true;
+  return h.pos && h.neg && h.count_parts && h.ncount > 0 && h.f && h.lnpart && h.part && (h.dx || !dx_needed);
+}
+static bool out_bwd_ok(const rs_sas_out_bwd_args* a) { return a && a->M > 0 && !a->o == !a->delta; }
+static bool in_bwd_ok(const rs_sas_in_bwd_args* a) { return a && a->M > 0; }
+
 }  // namespace rc
 
 extern "C" {
 
-int64_t rs_sas_block_parts(int64_t M) {
-  if (M <= 0) return 0;
-  return rc::grid_for(M);
-}
-
-int rs_sas_block_in(int64_t M, int64_t d, const void* x, int64_t ldx, const float* ln_w, const float* ln_b, float eps,
-                    void* Q, float* mean, float* rstd, const void* Wq, const float* bq, void* q, const void* Wkv,
-                    const float* bkv, void* kv, void* stream) {
-  if (M <= 0 || ldx % 8) return RS_ERR_ARG;
-  rc::InArgs a = {M, (const __bf16*)x, ldx, ln_w, ln_b, eps, (__bf16*)Q, mean, rstd, (const __bf16*)Wq, bq,
-                  (__bf16*)q, (const __bf16*)Wkv, bkv, (__bf16*)kv};
-  const dim3 grid((unsigned)rc::grid_for(M));
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) {
-    rc::set_lds(rc::block_in_kernel<64>, rc::lds_fwd<64>());
-    hipLaunchKernelGGL(rc::block_in_kernel<64>, grid, dim3(rc::NT), rc::lds_fwd<64>(), s, a);
-  } else if (d == 128) {
-    rc::set_lds(rc::block_in_kernel<128>, rc::lds_fwd<128>());
-    hipLaunchKernelGGL(rc::block_in_kernel<128>, grid, dim3(rc::NT), rc::lds_fwd<128>(), s, a);
-  } else {
-    return RS_ERR_UNSUPPORTED;
-  }
-  return (int)hipGetLastError();
-}
-
-int64_t rs_sas_block_in_count_parts(int64_t M) { return M > 0 ? rc::grid_for(M) : 0; }
-
-int rs_sas_block_in_embed(int64_t M, int64_t d, const int64_t* ids, int64_t T, const void* item_emb, const void* pos_emb,
-                          float scale, float drop_p, uint64_t salt, const uint64_t* seed_base, void* x0,
-                          const int64_t* count_ids, int* count_parts, const float* ln_w, const float* ln_b, float eps,
-                          void* Q, float* mean, float* rstd, const void* Wq, const float* bq, void* q, const void* Wkv,
-                          const float* bkv, void* kv, void* stream) {
-  if (M <= 0 || T <= 0 || M % T || !ids || !item_emb || !pos_emb || !x0 || !count_ids != !count_parts)
-    return RS_ERR_ARG;
-  if (((uintptr_t)item_emb | (uintptr_t)pos_emb | (uintptr_t)x0) % 16 || (d != 64 && d != 128)) return RS_ERR_ARG;
-  rc::InArgs a = {M, (const __bf16*)x0, d, ln_w, ln_b, eps, (__bf16*)Q, mean, rstd, (const __bf16*)Wq, bq,
-                  (__bf16*)q, (const __bf16*)Wkv, bkv, (__bf16*)kv,
-                  rc::EmbIn{ids, (const __bf16*)item_emb, (const __bf16*)pos_emb, T, scale, drop_p, salt, seed_base,
-                            (__bf16*)x0, count_ids, count_parts}};
-  const dim3 grid((unsigned)rc::grid_for(M));
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) {
-    rc::set_lds(rc::block_in_kernel<64>, rc::lds_fwd<64>());
-    hipLaunchKernelGGL(rc::block_in_kernel<64>, grid, dim3(rc::NT), rc::lds_fwd<64>(), s, a);
-  } else {
-    rc::set_lds(rc::block_in_kernel<128>, rc::lds_fwd<128>());
-    hipLaunchKernelGGL(rc::block_in_kernel<128>, grid, dim3(rc::NT), rc::lds_fwd<128>(), s, a);
-  }
-  return (int)hipGetLastError();
-}
-
-int rs_sas_block_out(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo, void* x1,
-                     const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
-                     const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
-                     const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2, const uint64_t* seed_base,
-                     void* stream) {
-  if (M <= 0) return RS_ERR_ARG;
-  rc::OutArgs a = {M, (const __bf16*)o, (const __bf16*)Q, (const __bf16*)Wo, bo, (__bf16*)x1, ln_w, ln_b, eps,
-                   (__bf16*)z, mean, rstd, (const __bf16*)W1, b1, (__bf16*)h1, (const __bf16*)W2, b2, (__bf16*)xn,
-                   ids, drop_p, salt1, salt2, seed_base};
-  return rc::launch_out(a, d, stream);
-}
-
 int64_t rs_sas_block_grid(int64_t M) { return M > 0 ? rc::grid_for(M) : 0; }
 
-int rs_sas_block_out_head(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo,
-                          void* x1, const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
-                          const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
-                          const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2,
-                          const uint64_t* seed_base, const void* E, const int64_t* pos, const int64_t* neg,
-                          const float* lnl_w, const float* lnl_b, const int* count_parts, int64_t ncount,
-                          const float* divisor, void* f, float* pl, float* nl, float* dpl, float* dnl, void* dx,
-                          float* lnpart, float* part, void* stream) {
-  if (M <= 0 || !E || !pos || !neg || !count_parts || ncount <= 0 || !f || !dx || !lnpart || !part) return RS_ERR_ARG;
-  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
-  rc::OutArgs a = {M, (const __bf16*)o, (const __bf16*)Q, (const __bf16*)Wo, bo, (__bf16*)x1, ln_w, ln_b, eps,
-                   (__bf16*)z, mean, rstd, (const __bf16*)W1, b1, (__bf16*)h1, (const __bf16*)W2, b2, (__bf16*)xn,
-                   ids, drop_p, salt1, salt2, seed_base,
-                   rc::HeadArgs{(const __bf16*)E, pos, neg, lnl_w, lnl_b, eps, count_parts, (int)ncount, divisor,
-                                (__bf16*)f, pl, nl, dpl, dnl, (__bf16*)dx, lnpart, part}};
+int rs_sas_block_boundary_fused(int64_t M, int64_t d) { return rc::boundary_fused(M, d) ? 1 : 0; }
+
+int rs_sas_block_in(int64_t d, const rs_sas_in_args* in, void* stream) {
+  if (!rc::in_ok(in, true)) return RS_ERR_ARG;
+  // (the embed form has no unfused sequence to fall back to)
+  if (!rc::width_ok(d)) return in->e.item_emb ? RS_ERR_ARG : RS_ERR_UNSUPPORTED;
+  rs_sas_in_args a = *in;
+  if (a.e.item_emb) {
+    a.x = a.e.x0;
+    a.ldx = d;
+  }
+  return rc::launch_in(a, d, stream);
+}
+
+int rs_sas_block_out(int64_t d, const rs_sas_out_args* out, void* stream) {
+  if (!rc::out_ok(out, true)) return RS_ERR_ARG;
+  if (!rc::width_ok(d)) return RS_ERR_UNSUPPORTED;
+  rs_sas_out_args a = *out;
+  if (a.h.E) a.h.eps = a.eps;
   return rc::launch_out(a, d, stream);
 }
 
+int rs_sas_block_out_bwd_delta(int64_t d, const rs_sas_out_bwd_args* out_bwd, void* stream) {
+  if (!rc::out_bwd_ok(out_bwd)) return RS_ERR_ARG;
+  if (!rc::width_ok(d)) return RS_ERR_UNSUPPORTED;
+  return rc::launch_out_bwd(*out_bwd, d, stream);
+}
+
+// the positional form without o / delta, kept for its callers: it fills the struct by field name
 int rs_sas_block_out_bwd(int64_t M, int64_t d, const void* dxn, const int64_t* ids, const void* h1, const void* x1,
                          const float* mean2, const float* rstd2, const float* ln_w, const void* W2T, const void* W1T,
                          const void* WoT, void* dy2, void* da1, void* dx1, void* dout, float* part, float drop_p,
                          uint64_t salt1, uint64_t salt2, const uint64_t* seed_base, void* stream) {
-  return rs_sas_block_out_bwd_delta(M, d, dxn, ids, h1, x1, mean2, rstd2, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout,
-                                    part, drop_p, salt1, salt2, seed_base, nullptr, nullptr, stream);
+  rs_sas_out_bwd_args a = {};
+  a.M = M, a.dxn = (const rs_bf16*)dxn, a.ids = ids, a.h1 = (const rs_bf16*)h1, a.x1 = (const rs_bf16*)x1;
+  a.mean2 = mean2, a.rstd2 = rstd2, a.ln_w = ln_w;
+  a.W2T = (const rs_bf16*)W2T, a.W1T = (const rs_bf16*)W1T, a.WoT = (const rs_bf16*)WoT;
+  a.dy2 = (rs_bf16*)dy2, a.da1 = (rs_bf16*)da1, a.dx1 = (rs_bf16*)dx1, a.dout = (rs_bf16*)dout, a.part = part;
+  a.drop_p = drop_p, a.salt1 = salt1, a.salt2 = salt2, a.seed_base = seed_base;
+  return rs_sas_block_out_bwd_delta(d, &a, stream);
 }
 
-int rs_sas_block_out_bwd_delta(int64_t M, int64_t d, const void* dxn, const int64_t* ids, const void* h1,
-                               const void* x1, const float* mean2, const float* rstd2, const float* ln_w,
-                               const void* W2T, const void* W1T, const void* WoT, void* dy2, void* da1, void* dx1,
-                               void* dout, float* part, float drop_p, uint64_t salt1, uint64_t salt2,
-                               const uint64_t* seed_base, const void* o, float* delta, void* stream) {
-  if (!o != !delta) return RS_ERR_ARG;
-  if (M <= 0) return RS_ERR_ARG;
-  rc::OutBwdArgs a = {M, (const __bf16*)dxn, ids, (const __bf16*)h1, (const __bf16*)x1, mean2, rstd2, ln_w,
-                      (const __bf16*)W2T, (const __bf16*)W1T, (const __bf16*)WoT, (__bf16*)dy2, (__bf16*)da1,
-                      (__bf16*)dx1, (__bf16*)dout, part, drop_p, salt1, salt2, seed_base, (const __bf16*)o, delta};
-  const dim3 grid((unsigned)rc::grid_for(M));
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) {
-    rc::set_lds(rc::block_out_bwd_kernel<64>, rc::lds_bwd<64>());
-    hipLaunchKernelGGL(rc::block_out_bwd_kernel<64>, grid, dim3(rc::NT), rc::lds_bwd<64>(), s, a);
-  } else if (d == 128) {
-    rc::set_lds(rc::block_out_bwd_kernel<128>, rc::lds_bwd<128>());
-    hipLaunchKernelGGL(rc::block_out_bwd_kernel<128>, grid, dim3(rc::NT), rc::lds_bwd<128>(), s, a);
-  } else {
-    return RS_ERR_UNSUPPORTED;
-  }
-  return (int)hipGetLastError();
+int rs_sas_block_in_bwd(int64_t d, const rs_sas_in_bwd_args* in_bwd, void* stream) {
+  if (!rc::in_bwd_ok(in_bwd)) return RS_ERR_ARG;
+  if (!rc::width_ok(d)) return RS_ERR_UNSUPPORTED;
+  if (in_bwd->ldwt != 3 * d) return RS_ERR_ARG;
+  return rc::launch_in_bwd(*in_bwd, d, stream);
 }
 
-int rs_sas_block_in_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
-                        const float* mean1, const float* rstd1, const float* ln_w, const void* WinT, void* dx,
-                        float* part, void* stream) {
-  if (M <= 0) return RS_ERR_ARG;
-  rc::InBwdArgs a = {M, (const __bf16*)dq, (const __bf16*)dkv, (const __bf16*)dx1, (const __bf16*)x, mean1, rstd1,
-                     ln_w, (const __bf16*)WinT, 3 * d, (__bf16*)dx, part};
-  const dim3 grid((unsigned)rc::grid_for(M));
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) {
-    rc::set_lds(rc::block_in_bwd_kernel<64>, rc::lds_bwd<64>());
-    hipLaunchKernelGGL(rc::block_in_bwd_kernel<64>, grid, dim3(rc::NT), rc::lds_bwd<64>(), s, a);
-  } else if (d == 128) {
-    rc::set_lds(rc::block_in_bwd_kernel<128>, rc::lds_bwd<128>());
-    hipLaunchKernelGGL(rc::block_in_bwd_kernel<128>, grid, dim3(rc::NT), rc::lds_bwd<128>(), s, a);
-  } else {
-    return RS_ERR_UNSUPPORTED;
-  }
-  return (int)hipGetLastError();
+int rs_sas_block_out_in(int64_t d, const rs_sas_out_args* out, const rs_sas_in_args* in, void* stream) {
+  if (!rc::out_ok(out, true) || !rc::in_ok(in, false) || out->h.E || in->e.item_emb || out->M != in->M)
+    return RS_ERR_ARG;
+  if (!rc::width_ok(d)) return RS_ERR_UNSUPPORTED;
+  const rs_sas_out_args a = *out;
+  rs_sas_in_args b = *in;
+  b.x = a.xn;
+  b.ldx = d;
+  if (rc::boundary_fused(a.M, d)) return rc::launch_out_in(a, b, d, stream);
+  const int rc1 = rc::launch_out(a, d, stream);
+  return rc1 ? rc1 : rc::launch_in(b, d, stream);
 }
 
-int rs_sas_block_boundary_fused(int64_t M, int64_t d) { return rc::boundary_fused(M, d) ? 1 : 0; }
-
-int rs_sas_block_out_in(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo, void* x1,
-                        const float* ln_w, const float* ln_b, float eps, void* z, float* mean, float* rstd,
-                        const void* W1, const float* b1, void* h1, const void* W2, const float* b2, void* xn,
-                        const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2, const uint64_t* seed_base,
-                        const float* ln1_w, const float* ln1_b, float eps1, void* Qn, float* mean1, float* rstd1,
-                        const void* Wq, const float* bq, void* q, const void* Wkv, const float* bkv, void* kv,
-                        void* stream) {
-  if (M <= 0) return RS_ERR_ARG;
-  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
-  if (!rc::boundary_fused(M, d)) {
-    const int rc1 = rs_sas_block_out(M, d, o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn,
-                                     ids, drop_p, salt1, salt2, seed_base, stream);
-    if (rc1) return rc1;
-    return rs_sas_block_in(M, d, xn, d, ln1_w, ln1_b, eps1, Qn, mean1, rstd1, Wq, bq, q, Wkv, bkv, kv, stream);
+int rs_sas_block_in_out_bwd(int64_t d, const rs_sas_in_bwd_args* in_bwd, const rs_sas_out_bwd_args* out_bwd,
+                            void* stream) {
+  if (!rc::in_bwd_ok(in_bwd) || !rc::out_bwd_ok(out_bwd) || in_bwd->M != out_bwd->M) return RS_ERR_ARG;
+  if (!rc::width_ok(d)) return RS_ERR_UNSUPPORTED;
+  if (in_bwd->ldwt != 3 * d) return RS_ERR_ARG;
+  rs_sas_in_bwd_args a = *in_bwd;
+  rs_sas_out_bwd_args b = *out_bwd;
+  if (rc::boundary_fused(a.M, d)) {
+    a.dx = nullptr;
+    b.dxn = nullptr;
+    return rc::launch_in_out_bwd(a, b, d, stream);
   }
-  rc::OutArgs a = {M, (const __bf16*)o, (const __bf16*)Q, (const __bf16*)Wo, bo, (__bf16*)x1, ln_w, ln_b, eps,
-                   (__bf16*)z, mean, rstd, (const __bf16*)W1, b1, (__bf16*)h1, (const __bf16*)W2, b2, (__bf16*)xn,
-                   ids, drop_p, salt1, salt2, seed_base};
-  rc::InArgs b = {M, (const __bf16*)xn, d, ln1_w, ln1_b, eps1, (__bf16*)Qn, mean1, rstd1, (const __bf16*)Wq, bq,
-                  (__bf16*)q, (const __bf16*)Wkv, bkv, (__bf16*)kv};
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) rc::launch_out_in_t<64>(a, b, s);
-  else rc::launch_out_in_t<128>(a, b, s);
-  return (int)hipGetLastError();
+  if (!a.dx) return RS_ERR_ARG;   // the scratch is needed (known only with the grid)
+  b.dxn = a.dx;
+  const int rc1 = rc::launch_in_bwd(a, d, stream);
+  return rc1 ? rc1 : rc::launch_out_bwd(b, d, stream);
 }
 
-int rs_sas_block_in_out_bwd(int64_t M, int64_t d, const void* dq, const void* dkv, const void* dx1, const void* x,
-                            const float* mean1, const float* rstd1, const float* ln1_w, const void* WinT, void* dx,
-                            float* part1, const int64_t* ids, const void* h1, const void* x1p, const float* mean2,
-                            const float* rstd2, const float* ln2_w, const void* W2T, const void* W1T, const void* WoT,
-                            void* dy2, void* da1, void* dx1p, void* dout, float* part2, float drop_p, uint64_t salt1,
-                            uint64_t salt2, const uint64_t* seed_base, const void* o, float* delta, void* stream) {
-  if (M <= 0 || !o != !delta) return RS_ERR_ARG;
-  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
-  if (!rc::boundary_fused(M, d)) {
-    if (!dx) return RS_ERR_ARG;
-    const int rc1 = rs_sas_block_in_bwd(M, d, dq, dkv, dx1, x, mean1, rstd1, ln1_w, WinT, dx, part1, stream);
-    if (rc1) return rc1;
-    return rs_sas_block_out_bwd_delta(M, d, dx, ids, h1, x1p, mean2, rstd2, ln2_w, W2T, W1T, WoT, dy2, da1, dx1p, dout,
-                                      part2, drop_p, salt1, salt2, seed_base, o, delta, stream);
+int rs_sas_block_out_head_bwd(int64_t d, const rs_sas_out_args* out, const rs_sas_out_bwd_args* out_bwd,
+                              void* stream) {
+  if (!rc::out_ok(out, false) || !out->h.E || !out_bwd || out->M != out_bwd->M) return RS_ERR_ARG;
+  if (!rc::width_ok(d)) return RS_ERR_UNSUPPORTED;
+  rs_sas_out_args a = *out;
+  rs_sas_out_bwd_args b = *out_bwd;
+  a.h.eps = a.eps;
+  b.ids = a.ids, b.h1 = a.h1, b.x1 = a.x1, b.mean2 = a.mean, b.rstd2 = a.rstd, b.ln_w = a.ln_w;
+  b.drop_p = a.drop_p, b.salt1 = a.salt1, b.salt2 = a.salt2, b.seed_base = a.seed_base;
+  if (rc::boundary_fused(a.M, d)) {
+    a.h.dx = nullptr;
+    b.dxn = nullptr;
+    b.o = a.o;
+    return rc::launch_out_head_bwd(a, b, d, stream);
   }
-  rc::InBwdArgs a = {M, (const __bf16*)dq, (const __bf16*)dkv, (const __bf16*)dx1, (const __bf16*)x, mean1, rstd1,
-                     ln1_w, (const __bf16*)WinT, 3 * d, nullptr, part1};
-  rc::OutBwdArgs b = {M, nullptr, ids, (const __bf16*)h1, (const __bf16*)x1p, mean2, rstd2, ln2_w,
-                      (const __bf16*)W2T, (const __bf16*)W1T, (const __bf16*)WoT, (__bf16*)dy2, (__bf16*)da1,
-                      (__bf16*)dx1p, (__bf16*)dout, part2, drop_p, salt1, salt2, seed_base, (const __bf16*)o, delta};
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) rc::launch_in_out_bwd_t<64>(a, b, s);
-  else rc::launch_in_out_bwd_t<128>(a, b, s);
-  return (int)hipGetLastError();
-}
-
-int rs_sas_block_out_head_bwd(int64_t M, int64_t d, const void* o, const void* Q, const void* Wo, const float* bo,
-                              void* x1, const float* ln_w, const float* ln_b, float eps, void* z, float* mean,
-                              float* rstd, const void* W1, const float* b1, void* h1, const void* W2, const float* b2,
-                              void* xn, const int64_t* ids, float drop_p, uint64_t salt1, uint64_t salt2,
-                              const uint64_t* seed_base, const void* E, const int64_t* pos, const int64_t* neg,
-                              const float* lnl_w, const float* lnl_b, const int* count_parts, int64_t ncount,
-                              const float* divisor, void* f, float* pl, float* nl, float* dpl, float* dnl, void* dx,
-                              float* lnpart, float* part, const void* W2T, const void* W1T, const void* WoT, void* dy2,
-                              void* da1, void* dx1, void* dout, float* part2, float* delta, void* stream) {
-  if (M <= 0 || !E || !pos || !neg || !count_parts || ncount <= 0 || !f || !lnpart || !part) return RS_ERR_ARG;
-  if (d != 64 && d != 128) return RS_ERR_UNSUPPORTED;
-  if (!rc::boundary_fused(M, d)) {
-    if (!dx) return RS_ERR_ARG;
-    const int rc1 = rs_sas_block_out_head(M, d, o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn,
-                                          ids, drop_p, salt1, salt2, seed_base, E, pos, neg, lnl_w, lnl_b, count_parts,
-                                          ncount, divisor, f, pl, nl, dpl, dnl, dx, lnpart, part, stream);
-    if (rc1) return rc1;
-    return rs_sas_block_out_bwd_delta(M, d, dx, ids, h1, x1, mean, rstd, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout,
-                                      part2, drop_p, salt1, salt2, seed_base, delta ? o : nullptr, delta, stream);
-  }
-  rc::OutArgs a = {M, (const __bf16*)o, (const __bf16*)Q, (const __bf16*)Wo, bo, (__bf16*)x1, ln_w, ln_b, eps,
-                   (__bf16*)z, mean, rstd, (const __bf16*)W1, b1, (__bf16*)h1, (const __bf16*)W2, b2, (__bf16*)xn,
-                   ids, drop_p, salt1, salt2, seed_base,
-                   rc::HeadArgs{(const __bf16*)E, pos, neg, lnl_w, lnl_b, eps, count_parts, (int)ncount, divisor,
-                                (__bf16*)f, pl, nl, dpl, dnl, nullptr, lnpart, part}};
-  rc::OutBwdArgs b = {M, nullptr, ids, (const __bf16*)h1, (const __bf16*)x1, mean, rstd, ln_w, (const __bf16*)W2T,
-                      (const __bf16*)W1T, (const __bf16*)WoT, (__bf16*)dy2, (__bf16*)da1, (__bf16*)dx1, (__bf16*)dout,
-                      part2, drop_p, salt1, salt2, seed_base, (const __bf16*)o, delta};
-  hipStream_t s = (hipStream_t)stream;
-  if (d == 64) rc::launch_out_head_bwd_t<64>(a, b, s);
-  else rc::launch_out_head_bwd_t<128>(a, b, s);
-  return (int)hipGetLastError();
+  if (!a.h.dx) return RS_ERR_ARG;   // the scratch is needed (known only with the grid)
+  b.dxn = a.h.dx;
+  b.o = b.delta ? a.o : nullptr;
+  const int rc1 = rc::launch_out(a, d, stream);
+  return rc1 ? rc1 : rc::launch_out_bwd(b, d, stream);
 }
 
 int rs_transpose_bf16(int64_t nmat, const int64_t* desc, int64_t max_tiles, const void* src, void* dst,

@@ -9,12 +9,12 @@ as HIP kernels through the C ABI, orchestrated by :class:`SASEngine`:
 bf16 fused step (FusedTrainStep, d in {64, 128}: the benchmarked path) -- per block two row-chain kernels per
 direction (rowchain.hip: one workgroup per CU, the block's three d x d weights in LDS, each wave carrying 16-token
 tiles through the sublayer chain in registers) around the LDS-resident attention (attention_lds.hip):
-  x = emb*sqrt(d)+pos, drop, mask;  Q = LN1(x);      rs_sas_block_in_embed (first block) / rs_sas_block_in
+  x = emb*sqrt(d)+pos, drop, mask;  Q = LN1(x);      rs_sas_block_in (first block: with rs_sas_embed_args)
   q = Q Wq^T+bq;  kv = x Wkv^T+bkv                   (same launch; sas.py:59-67, 73-76)
   o = attn(q, k, v) causal, dropout on P             rs_attn_fwd (mask_kind 0; sas.py:75)
   x1 = Q + o Wo^T + bo;  z = LN2(x1);                rs_sas_block_out (sas.py:75-84, PointWiseFeedForward)
   x = (drop(relu(drop(z W1^T+b1)) W2^T+b2) + z)*m    (same launch)
-  f = LN(x); pl/nl = <f, E[pos/neg]>; BCE + grads   rs_sas_block_out_head (the last block's output kernel)
+  f = LN(x); pl/nl = <f, E[pos/neg]>; BCE + grads   rs_sas_block_out with rs_sas_head_args (the last block)
 backward: rs_sas_block_out_bwd_delta -> rs_attn_bwd (dQ and dK/dV workgroups in one launch) ->
 rs_sas_block_in_bwd per block (between two blocks one launch carries both adjacent row chains: rs_sas_block_out_in
 forward, rs_sas_block_in_out_bwd backward; in the fused training step the last block's output chain, the head and
@@ -318,7 +318,7 @@ class SASEngine:
     def forward(self, ids, pos, neg, training, need_logits=True, clone_seed=True, fuse_head=False,
                 head_divisor=None, ce=False):
         """fuse_head (the fused training step, whose backward forms the BCE gradient itself): the head's forward
-        and backward run as one pass per token inside the last block's output kernel (rs_sas_block_out_head); the
+        and backward run as one pass per token inside the last block's output kernel (rs_sas_block_out with a head); the
         returned pl / nl are filled by then.  The first block's input kernel counts the valid positions (the BCE
         divisor) for it; head_divisor (device scalar, data parallel: 1) replaces that count and must be the divisor
         later passed to backward.  ce (ce_forward): the blocks only -- no last LayerNorm, no sampled head; the

@@ -513,69 +513,13 @@ def sas_block_fused_ok(d, dtype):
     return dtype == torch.bfloat16 and d in (64, 128)
 
 
-def sas_block_in(x, ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv):
-    M, d = x.shape
-    call("rs_sas_block_in", M, d, ptr(x), ld(x), ptr(ln_w), ptr(ln_b), eps, ptr(Q), ptr(mean), ptr(rstd),
-         ptr(Wq), ptr(bq), ptr(q), ptr(Wkv), ptr(bkv), ptr(kv), stream())
-
-
-def sas_block_in_count_parts(M):
-    return int(_lib.lib().rs_sas_block_in_count_parts(M))
-
-
-def sas_block_in_embed(ids, T, item_emb, pos_emb, scale, drop_p, salt, seed_base, x0, count_ids, count_parts,
-                       ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv):
-    """embed_fwd(_counted) (mode 0) + sas_block_in in one launch (rowchain); x0 receives the embedding output."""
-    M, d = x0.shape
-    assert ids.numel() == M and item_emb.dtype == torch.bfloat16 and x0.dtype == torch.bfloat16
-    if count_parts is not None:
-        assert count_parts.dtype == torch.int32 and count_parts.numel() >= sas_block_in_count_parts(M)
-    call("rs_sas_block_in_embed", M, d, ptr(ids), T, ptr(item_emb), ptr(pos_emb), scale, drop_p, salt,
-         ptr(seed_base), ptr(x0), ptr(count_ids), ptr(count_parts), ptr(ln_w), ptr(ln_b), eps, ptr(Q), ptr(mean),
-         ptr(rstd), ptr(Wq), ptr(bq), ptr(q), ptr(Wkv), ptr(bkv), ptr(kv), stream())
-
-
 def sas_block_grid(M):
+    """Workgroups the row-chain kernels launch for M rows = per-workgroup partial sets (LayerNorm affine partials,
+    BCE partials, valid-position counts) they write."""
     return int(_lib.lib().rs_sas_block_grid(M))
 
 
-def sas_block_out_head(out_args, E, pos, neg, lnl_w, lnl_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart,
-                       part):
-    """sas_block_out(*out_args) for the last block with the SAS head in the same launch (rowchain);
-    lnpart [G][2][d], part [G][3] with G = sas_block_grid(M)."""
-    (o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
-     seed_base) = out_args
-    M, d = o.shape
-    G = sas_block_grid(M)
-    assert part.numel() == 3 * G and lnpart.numel() >= 2 * d * G and count_parts.dtype == torch.int32
-    call("rs_sas_block_out_head", M, d, ptr(o), ptr(Q), ptr(Wo), ptr(bo), ptr(x1), ptr(ln_w), ptr(ln_b), eps, ptr(z),
-         ptr(mean), ptr(rstd), ptr(W1), ptr(b1), ptr(h1), ptr(W2), ptr(b2), ptr(xn), ptr(ids), drop_p, salt1, salt2,
-         ptr(seed_base), ptr(E), ptr(pos), ptr(neg), ptr(lnl_w), ptr(lnl_b), ptr(count_parts), count_parts.numel(),
-         ptr(divisor), ptr(f), ptr(pl), ptr(nl), ptr(dpl), ptr(dnl), ptr(dx), ptr(lnpart), ptr(part), stream())
-
-
-def sas_block_out(o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p,
-                  salt1, salt2, seed_base):
-    M, d = o.shape
-    call("rs_sas_block_out", M, d, ptr(o), ptr(Q), ptr(Wo), ptr(bo), ptr(x1), ptr(ln_w), ptr(ln_b), eps, ptr(z),
-         ptr(mean), ptr(rstd), ptr(W1), ptr(b1), ptr(h1), ptr(W2), ptr(b2), ptr(xn), ptr(ids), drop_p, salt1,
-         salt2, ptr(seed_base), stream())
-
-
-def sas_block_out_bwd(dxn, ids, h1, x1, mean2, rstd2, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout, part, drop_p, salt1,
-                      salt2, seed_base, o=None, delta=None):
-    """part: fp32 >= 2*d*sas_block_parts(M), receives the LN2 affine partials (ln_partial_segments).  o, delta
-    (one-head attention output [M, d] bf16, fp32 [M]): also delta = rowsum(dout * o) for attn_bwd(delta_in=True)."""
-    M, d = dxn.shape
-    call("rs_sas_block_out_bwd_delta", M, d, ptr(dxn), ptr(ids), ptr(h1), ptr(x1), ptr(mean2), ptr(rstd2),
-         ptr(ln_w), ptr(W2T), ptr(W1T), ptr(WoT), ptr(dy2), ptr(da1), ptr(dx1), ptr(dout), ptr(part), drop_p, salt1,
-         salt2, ptr(seed_base), ptr(o), ptr(delta), stream())
-
-
-def sas_block_in_bwd(dq, dkv, dx1, x, mean1, rstd1, ln_w, WinT, dx, part):
-    M, d = dq.shape
-    call("rs_sas_block_in_bwd", M, d, ptr(dq), ptr(dkv), ptr(dx1), ptr(x), ptr(mean1), ptr(rstd1), ptr(ln_w),
-         ptr(WinT), ptr(dx), ptr(part), stream())
+sas_block_parts = sas_block_in_count_parts = sas_block_grid      # the names the partial-set count had per kernel
 
 
 def sas_block_boundary_fused(M, d):
@@ -584,30 +528,112 @@ def sas_block_boundary_fused(M, d):
     return bool(_lib.lib().rs_sas_block_boundary_fused(M, d))
 
 
+# The C entries take argument structs (include/recsys_hip.h documents the fields).  The wrappers below keep their
+# tensor-level signatures; each argument group is mapped to its struct's field names in exactly one place:
+def _sas_args(cls, **fields):
+    return cls(**{k: ptr(v) if isinstance(v, torch.Tensor) else v for k, v in fields.items() if v is not None})
+
+
+def _sas_in(x, ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv, embed=None):
+    return _sas_args(_lib.SasInArgs, M=x.shape[0], x=x, ldx=ld(x), ln_w=ln_w, ln_b=ln_b, eps=eps, Q=Q, mean=mean,
+                     rstd=rstd, Wq=Wq, bq=bq, q=q, Wkv=Wkv, bkv=bkv, kv=kv, e=embed)
+
+
+def _sas_out(o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
+             seed_base, head=None):
+    return _sas_args(_lib.SasOutArgs, M=o.shape[0], o=o, Q=Q, Wo=Wo, bo=bo, x1=x1, ln_w=ln_w, ln_b=ln_b, eps=eps,
+                     z=z, mean=mean, rstd=rstd, W1=W1, b1=b1, h1=h1, W2=W2, b2=b2, xn=xn, ids=ids, drop_p=drop_p,
+                     salt1=salt1, salt2=salt2, seed_base=seed_base, h=head)
+
+
+def _sas_head(M, d, E, pos, neg, ln_w, ln_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart, part):
+    G = sas_block_grid(M)
+    assert part.numel() == 3 * G and lnpart.numel() >= 2 * d * G and count_parts.dtype == torch.int32
+    return _sas_args(_lib.SasHeadArgs, E=E, pos=pos, neg=neg, ln_w=ln_w, ln_b=ln_b, count_parts=count_parts,
+                     ncount=count_parts.numel(), divisor=divisor, f=f, pl=pl, nl=nl, dpl=dpl, dnl=dnl, dx=dx,
+                     lnpart=lnpart, part=part)
+
+
+def _sas_out_bwd(M, dxn, ids, h1, x1, mean2, rstd2, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout, part, drop_p, salt1,
+                 salt2, seed_base, o=None, delta=None):
+    return _sas_args(_lib.SasOutBwdArgs, M=M, dxn=dxn, ids=ids, h1=h1, x1=x1, mean2=mean2, rstd2=rstd2, ln_w=ln_w,
+                     W2T=W2T, W1T=W1T, WoT=WoT, dy2=dy2, da1=da1, dx1=dx1, dout=dout, part=part, drop_p=drop_p,
+                     salt1=salt1, salt2=salt2, seed_base=seed_base, o=o, delta=delta)
+
+
+def _sas_in_bwd(dq, dkv, dx1, x, mean1, rstd1, ln_w, WinT, dx, part):
+    return _sas_args(_lib.SasInBwdArgs, M=dq.shape[0], dq=dq, dkv=dkv, dx1=dx1, x=x, mean1=mean1, rstd1=rstd1,
+                     ln_w=ln_w, WinT=WinT, ldwt=ld(WinT), dx=dx, part=part)
+
+
+def sas_block_in(x, ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv):
+    a = _sas_in(x, ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv)
+    call("rs_sas_block_in", x.shape[1], C.byref(a), stream())
+
+
+def sas_block_in_embed(ids, T, item_emb, pos_emb, scale, drop_p, salt, seed_base, x0, count_ids, count_parts,
+                       ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv):
+    """embed_fwd(_counted) (mode 0) + sas_block_in in one launch (rowchain); x0 receives the embedding output."""
+    M, d = x0.shape
+    assert ids.numel() == M and item_emb.dtype == torch.bfloat16 and x0.dtype == torch.bfloat16
+    if count_parts is not None:
+        assert count_parts.dtype == torch.int32 and count_parts.numel() >= sas_block_grid(M)
+    e = _sas_args(_lib.SasEmbedArgs, ids=ids, item_emb=item_emb, pos_emb=pos_emb, T=T, scale=scale, drop_p=drop_p,
+                  salt=salt, seed_base=seed_base, x0=x0, count_ids=count_ids, count_parts=count_parts)
+    a = _sas_in(x0, ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv, embed=e)
+    call("rs_sas_block_in", d, C.byref(a), stream())
+
+
+def sas_block_out_head(out_args, E, pos, neg, lnl_w, lnl_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart,
+                       part):
+    """sas_block_out(*out_args) for the last block with the SAS head in the same launch (rowchain);
+    lnpart [G][2][d], part [G][3] with G = sas_block_grid(M)."""
+    M, d = out_args[0].shape
+    h = _sas_head(M, d, E, pos, neg, lnl_w, lnl_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart, part)
+    a = _sas_out(*out_args, head=h)
+    call("rs_sas_block_out", d, C.byref(a), stream())
+
+
+def sas_block_out(o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p,
+                  salt1, salt2, seed_base):
+    a = _sas_out(o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
+                 seed_base)
+    call("rs_sas_block_out", o.shape[1], C.byref(a), stream())
+
+
+def sas_block_out_bwd(dxn, ids, h1, x1, mean2, rstd2, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout, part, drop_p, salt1,
+                      salt2, seed_base, o=None, delta=None):
+    """part: fp32 >= 2*d*sas_block_grid(M), receives the LN2 affine partials (ln_partial_segments).  o, delta
+    (one-head attention output [M, d] bf16, fp32 [M]): also delta = rowsum(dout * o) for attn_bwd(delta_in=True)."""
+    M, d = dxn.shape
+    a = _sas_out_bwd(M, dxn, ids, h1, x1, mean2, rstd2, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout, part, drop_p, salt1,
+                     salt2, seed_base, o, delta)
+    call("rs_sas_block_out_bwd_delta", d, C.byref(a), stream())
+
+
+def sas_block_in_bwd(dq, dkv, dx1, x, mean1, rstd1, ln_w, WinT, dx, part):
+    a = _sas_in_bwd(dq, dkv, dx1, x, mean1, rstd1, ln_w, WinT, dx, part)
+    call("rs_sas_block_in_bwd", dq.shape[1], C.byref(a), stream())
+
+
 def sas_block_out_in(out_args, ln1_w, ln1_b, eps1, Qn, mean1, rstd1, Wq, bq, q, Wkv, bkv, kv):
     """sas_block_out(*out_args) of block i, then sas_block_in(xn, ...) of block i+1 on the tile in registers: one
     launch (rowchain), bitwise the two calls' results."""
-    (o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
-     seed_base) = out_args
-    M, d = o.shape
-    call("rs_sas_block_out_in", M, d, ptr(o), ptr(Q), ptr(Wo), ptr(bo), ptr(x1), ptr(ln_w), ptr(ln_b), eps, ptr(z),
-         ptr(mean), ptr(rstd), ptr(W1), ptr(b1), ptr(h1), ptr(W2), ptr(b2), ptr(xn), ptr(ids), drop_p, salt1, salt2,
-         ptr(seed_base), ptr(ln1_w), ptr(ln1_b), eps1, ptr(Qn), ptr(mean1), ptr(rstd1), ptr(Wq), ptr(bq), ptr(q),
-         ptr(Wkv), ptr(bkv), ptr(kv), stream())
+    a = _sas_out(*out_args)
+    # block i+1's input side on the same rows: the entry sets its x / ldx to the first chain's xn / d
+    b = _sas_args(_lib.SasInArgs, M=a.M, ln_w=ln1_w, ln_b=ln1_b, eps=eps1, Q=Qn, mean=mean1, rstd=rstd1, Wq=Wq,
+                  bq=bq, q=q, Wkv=Wkv, bkv=bkv, kv=kv)
+    call("rs_sas_block_out_in", out_args[0].shape[1], C.byref(a), C.byref(b), stream())
 
 
 def sas_block_in_out_bwd(in_args, dx, part1, out_args):
     """sas_block_in_bwd(*in_args, dx, part1) of block i, then sas_block_out_bwd(dx, *out_args) of block i-1 on the
     tile in registers: one launch (rowchain), bitwise the two calls' results except that dx is not written.  dx: the
     scratch of the two-launch path, None allowed where sas_block_boundary_fused(M, d)."""
-    dq, dkv, dx1, x, mean1, rstd1, ln1_w, WinT = in_args
-    (ids, h1, x1, mean2, rstd2, ln2_w, W2T, W1T, WoT, dy2, da1, dx1o, dout, part2, drop_p, salt1, salt2,
-     seed_base, o, delta) = out_args
-    M, d = dq.shape
-    call("rs_sas_block_in_out_bwd", M, d, ptr(dq), ptr(dkv), ptr(dx1), ptr(x), ptr(mean1), ptr(rstd1), ptr(ln1_w),
-         ptr(WinT), ptr(dx), ptr(part1), ptr(ids), ptr(h1), ptr(x1), ptr(mean2), ptr(rstd2), ptr(ln2_w), ptr(W2T),
-         ptr(W1T), ptr(WoT), ptr(dy2), ptr(da1), ptr(dx1o), ptr(dout), ptr(part2), drop_p, salt1, salt2,
-         ptr(seed_base), ptr(o), ptr(delta), stream())
+    M, d = in_args[0].shape
+    a = _sas_in_bwd(*in_args, dx, part1)
+    b = _sas_out_bwd(M, None, *out_args)
+    call("rs_sas_block_in_out_bwd", d, C.byref(a), C.byref(b), stream())
 
 
 def sas_block_out_head_bwd(out_args, head_args, W2T, W1T, WoT, dy2, da1, dx1, dout, part2, delta=None):
@@ -615,19 +641,13 @@ def sas_block_out_head_bwd(out_args, head_args, W2T, W1T, WoT, dy2, da1, dx1, do
     x1, mean, rstd, ln_w, W2T, W1T, WoT, dy2, da1, dx1, dout, part2, ..., o, delta) on the tile in registers: one
     launch (rowchain), bitwise the two calls' results except that dx is not written.  head_args' dx: the scratch of
     the two-launch path, None allowed where sas_block_boundary_fused(M, d)."""
-    (o, Q, Wo, bo, x1, ln_w, ln_b, eps, z, mean, rstd, W1, b1, h1, W2, b2, xn, ids, drop_p, salt1, salt2,
-     seed_base) = out_args
-    E, pos, neg, lnl_w, lnl_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart, part = head_args
-    M, d = o.shape
-    G = sas_block_grid(M)
-    assert part.numel() == 3 * G and lnpart.numel() >= 2 * d * G and count_parts.dtype == torch.int32
-    assert part2.numel() >= 2 * d * G
-    call("rs_sas_block_out_head_bwd", M, d, ptr(o), ptr(Q), ptr(Wo), ptr(bo), ptr(x1), ptr(ln_w), ptr(ln_b), eps,
-         ptr(z), ptr(mean), ptr(rstd), ptr(W1), ptr(b1), ptr(h1), ptr(W2), ptr(b2), ptr(xn), ptr(ids), drop_p, salt1,
-         salt2, ptr(seed_base), ptr(E), ptr(pos), ptr(neg), ptr(lnl_w), ptr(lnl_b), ptr(count_parts),
-         count_parts.numel(), ptr(divisor), ptr(f), ptr(pl), ptr(nl), ptr(dpl), ptr(dnl), ptr(dx), ptr(lnpart),
-         ptr(part), ptr(W2T), ptr(W1T), ptr(WoT), ptr(dy2), ptr(da1), ptr(dx1), ptr(dout), ptr(part2), ptr(delta),
-         stream())
+    M, d = out_args[0].shape
+    assert part2.numel() >= 2 * d * sas_block_grid(M)
+    a = _sas_out(*out_args, head=_sas_head(M, d, *head_args))
+    # the entry takes the saved tensors, mask, seeds and o of the backward from the forward's arguments
+    b = _sas_args(_lib.SasOutBwdArgs, M=M, W2T=W2T, W1T=W1T, WoT=WoT, dy2=dy2, da1=da1, dx1=dx1, dout=dout,
+                  part=part2, delta=delta)
+    call("rs_sas_block_out_head_bwd", d, C.byref(a), C.byref(b), stream())
 
 
 # ---- union-of-touched-rows table-gradient exchange (sparse_rows.hip) -------------------------
@@ -653,15 +673,10 @@ def rows_unpack(dst, index, compact):
     call("rs_rows_unpack", ptr(dst), rows, d, ptr(index), ptr(compact), stream())
 
 
-def sas_block_parts(M):
-    """LayerNorm affine partial sets written by rs_sas_block_out_bwd / rs_sas_block_in_bwd for M rows."""
-    return int(_lib.lib().rs_sas_block_parts(M))
-
-
 def ln_partial_segments(part, M, d, dgamma, dbeta, nb=None):
     """The two reduce segments of a fused kernel's LayerNorm partials (part[b][2][d], b < nb; default: the
     SAS row-block backward kernels' set count)."""
-    nb = sas_block_parts(M) if nb is None else nb
+    nb = sas_block_grid(M) if nb is None else nb
     return [(part, 2 * d, nb, d, dgamma), (part[d:], 2 * d, nb, d, dbeta)]
 
 

@@ -154,7 +154,7 @@ def test_header_declares_and_lib_binds_the_head():
     assert L.RESTYPES["rs_sas_sce_ws_bytes"] is L.C.c_int64
     for name in ("sas_sce_fwd", "sas_sce_bwd", "sas_sce_ws_numel", "sas_sce_max_k", "uniform_items"):
         assert callable(getattr(ops, name))
-    assert L.lib().rs_abi_version() == 1
+    assert L.lib().rs_abi_version() == 2
 
 
 def test_workspace_is_sized_by_cap_k_d_alone():

@@ -19,7 +19,7 @@ static void pct(const char* name, std::vector<double> v) {
 
 int main(int argc, char** argv) {
   const int64_t M = argc > 1 ? atoll(argv[1]) : 25600, d = 128;
-  void *o, *Q, *W, *x1, *z, *h1, *xn;
+  __bf16 *o, *Q, *W, *x1, *z, *h1, *xn;
   float *b, *lw, *lb, *mu, *rs;
   int64_t* ids;
   uint64_t* sb;
@@ -30,11 +30,10 @@ int main(int argc, char** argv) {
   hipMemset(o, 0x3c, M * d * 2); hipMemset(Q, 0x3c, M * d * 2); hipMemset(W, 0x3c, 3 * d * d * 2);
   hipMemset(b, 0, d * 4); hipMemset(lw, 0, d * 4); hipMemset(lb, 0, d * 4); hipMemset(ids, 1, M * 8);
   hipMemset(sb, 0, 8);
-  const __bf16* Wb = (const __bf16*)W;
-  // --head (argv[2] = "head"): the last block's kernel with the SAS head (rs_sas_block_out_head), 3,416 items
+  // --head (argv[2] = "head"): the last block's kernel with the SAS head (rs_sas_out_args.h), 3,416 items
   const bool head = argc > 2 && std::string(argv[2]) == "head";
   const int G = (int)rc::grid_for(M);
-  void *E, *f, *dx;
+  __bf16 *E, *f, *dx;
   int64_t *pos, *neg;
   int* cnt;
   float *pl, *nl, *dpl, *dnl, *lnpart, *part;
@@ -51,6 +50,15 @@ int main(int argc, char** argv) {
     hipMemcpy(cnt, c.data(), G * 4, hipMemcpyHostToDevice);
     hipMemset(E, 0x3c, 3417 * d * 2);
   }
+  rs_sas_out_args a = {};
+  a.M = M, a.o = o, a.Q = Q, a.Wo = W, a.bo = b, a.x1 = x1, a.ln_w = lw, a.ln_b = lb, a.eps = 1e-8f, a.z = z;
+  a.mean = mu, a.rstd = rs, a.W1 = W + d * d, a.b1 = b, a.h1 = h1, a.W2 = W + 2 * d * d, a.b2 = b, a.xn = xn;
+  a.ids = ids, a.drop_p = 0.2f, a.salt1 = 3, a.salt2 = 5, a.seed_base = sb;
+  if (head) {
+    rs_sas_head_args& h = a.h;
+    h.E = E, h.pos = pos, h.neg = neg, h.ln_w = lw, h.ln_b = lb, h.count_parts = cnt, h.ncount = G, h.f = f;
+    h.pl = pl, h.nl = nl, h.dpl = dpl, h.dnl = dnl, h.dx = dx, h.lnpart = lnpart, h.part = part;
+  }
   std::vector<unsigned long long> p(4096 * 8 * 16);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
@@ -58,13 +66,7 @@ int main(int argc, char** argv) {
   for (int it = 0; it < 20; ++it) {
     hipMemcpyToSymbol(HIP_SYMBOL(rc::g_rc_prof), p.data(), p.size() * 8);   // zero
     hipEventRecord(e0, 0);
-    if (head)
-      rs_sas_block_out_head(M, d, o, Q, Wb, b, x1, lw, lb, 1e-8f, z, mu, rs, Wb + d * d, b, h1, Wb + 2 * d * d, b, xn,
-                            ids, 0.2f, 3, 5, sb, E, pos, neg, lw, lb, cnt, G, nullptr, f, pl, nl, dpl, dnl, dx,
-                            lnpart, part, 0);
-    else
-      rs_sas_block_out(M, d, o, Q, Wb, b, x1, lw, lb, 1e-8f, z, mu, rs, Wb + d * d, b, h1, Wb + 2 * d * d, b, xn,
-                       ids, 0.2f, 3, 5, sb, 0);
+    rs_sas_block_out(d, &a, 0);
     hipEventRecord(e1, 0);
     hipEventSynchronize(e1);
     hipEventElapsedTime(&ms, e0, e1);
