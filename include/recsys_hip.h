@@ -876,6 +876,32 @@ int rs_sas_sce_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ld
 int rs_uniform_items(const uint64_t* seed_base, uint64_t salt, int64_t item_num, int64_t K, int64_t* out,
                      void* stream);
 
+/* ---- the same sampled-softmax head for an untied output layer with a bias (sas_sce.hip; BERT4Rec's out) ----
+ * E: any [V1][d] table in hl's dtype, bias: fp32 [V1] or NULL.  The definition above with
+ *   z_r0 = <h_r, E[lab_r]> + b[lab_r],   z_rj = <h_r, E[cand_j]> + b[cand_j]
+ * live, the loss, dh, coef, pg, dEc and keys exactly as above on these logits, and in addition
+ *   dbc[j] = s sum_r p_rj        fp32 [K]: the bias gradient at cand_j, the rows summed in a fixed order (the dEc
+ *                                launch's row splits in slabs reduced in split order; no atomics)
+ * The bias gradient at the positive is coef[r]: db[v] += the entries of {coef, dbc} keyed v, over the same keys (one
+ * writer per element: rs_item_grad_f32 at d = 1 on the index built for {pg, dEc}, radix path).
+ * dbc is required with a bias and must be NULL without one (RS_ERR_ARG).  bias == NULL gives the rs_sas_sce_* entries'
+ * bits on every output and in ws wherever both run the same kernel (fp32, and bf16 up to d = 128).
+ * rs_sce_head_path (host only): 1 = the MFMA sweep (fp32 d <= 128; bf16 d <= 256, padded to 64 / 128 / 256 in the
+ * fragments), 0 = the plain kernel (wider rows up to 1024), < 0 = unsupported dtype / width.
+ * ws: rs_sce_head_ws_bytes(dtype, cap, K, d, has_bias) bytes (host only; rs_sas_sce_ws_bytes plus the dbc slabs with a
+ * bias; nothing is sized by V1), 16-byte aligned; dh: rs_sce_head_dh_splits(dtype, cap, K, d) slabs.  Argument
+ * checks, limits and return codes as rs_sas_sce_fwd / _bwd. */
+int64_t rs_sce_head_ws_bytes(int dtype, int64_t cap, int64_t K, int64_t d, int has_bias);
+int64_t rs_sce_head_dh_splits(int dtype, int64_t cap, int64_t K, int64_t d);
+int rs_sce_head_path(int dtype, int64_t d);
+int rs_sce_head_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                    const int32_t* count, const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K,
+                    const float* divisor, void* ws, float* out, void* stream);
+int rs_sce_head_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                    const int32_t* count, const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K,
+                    const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
+                    float* dbc, int64_t* keys, void* stream);
+
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);
 /* sizeof of the structs of this header that bindings mirror (host only); -1 for an unknown index. */

@@ -201,6 +201,12 @@ SIGNATURES = {
     "rs_sas_sce_fwd": [i32, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp],
     "rs_sas_sce_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "rs_uniform_items": [vp, u64, i64, i64, vp, vp],
+    "rs_sce_head_ws_bytes": [i32, i64, i64, i64, i32],
+    "rs_sce_head_dh_splits": [i32, i64, i64, i64],
+    "rs_sce_head_path": [i32, i64],
+    "rs_sce_head_fwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp],
+    "rs_sce_head_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                        vp],
     "rs_kernel_stamps": [vp, vp, i32],
     "rs_kernel_stamp_count": [],
     "rs_kernel_stamp_kinds": [C.POINTER(i32), i32],
@@ -216,7 +222,8 @@ RESTYPES = {"rs_wgrad_grouped_slab_numel": C.c_int64, "rs_abi_sizeof": C.c_int64
             "rs_vocab_ce_ws_numel": C.c_int64, "rs_full_ws_bytes": C.c_int64,
             "rs_sas_block_grid": C.c_int64, "rs_layernorm_bwd_nparts": C.c_int64,
             "rs_sas_ce_rows_nparts": C.c_int64, "rs_sas_sce_max_k": C.c_int64,
-            "rs_sas_sce_ws_bytes": C.c_int64, "rs_sas_sce_dh_splits": C.c_int64}
+            "rs_sas_sce_ws_bytes": C.c_int64, "rs_sas_sce_dh_splits": C.c_int64,
+            "rs_sce_head_ws_bytes": C.c_int64, "rs_sce_head_dh_splits": C.c_int64}
 
 _lib = None
 

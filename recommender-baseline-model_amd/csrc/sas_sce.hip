@@ -29,6 +29,15 @@
 // The logits are never stored.  Widths: d <= 128 (padded with zeros to 64 or 128 in the fragments), fp32 or bf16
 // (bf16: d % 8 == 0); d in {64, 128} with aligned rows loads 16 bytes at a time.  128 < d <= 1024: generic_kernel,
 // the same sweep with plain FMA (below).
+//
+// The rs_sce_head_* entries run the same kernels for an untied output layer E [V1][d] with a bias b [V1] (BERT4Rec's
+// out.weight / out.bias): z_r0 = <h_r, E[lab_r]> + b[lab_r], z_rj = <h_r, E[cand_j]> + b[cand_j]; everything else is
+// computed on these logits as above, and the dEc role also leaves dbc[j] = s sum_r p_rj (each lane's live p summed
+// over its swept rows in sweep order, the four lane groups by two shuffles, the row splits through slabs reduced in
+// split order: no atomics).  The bias gradient at the positive is coef[r].  They also take bf16 128 < d <= 256 on the
+// MFMA sweep (DP = 256: 8 stationary fragments, 16 accumulators per lane, a 33 KB LDS tile); fp32 would need a 67 KB
+// tile and stays on generic_kernel past 128.  Without a bias they give the rs_sas_sce_* entries' bits wherever both run
+// the same kernel.
 #include "common.h"
 #include "../../include/recsys_hip.h"
 
@@ -63,6 +72,8 @@ struct Args {
   float* pg;
   float* slab;
   int64_t rows_per_split;
+  const float* bias;   // [V1] or null: added to every logit (rs_sce_head_*)
+  float* dbslab;       // dEc role: sum over the split's rows of p per candidate, [splits][K]; null without a bias
 };
 
 __device__ __forceinline__ int32_t clamp_id(int64_t v, int64_t V1) { return (v <= 0 || v >= V1) ? 0 : (int32_t)v; }
@@ -96,6 +107,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
   __shared__ float sWlse[TS];
   __shared__ int32_t sSid[TS];
   __shared__ float sScoef[TS];
+  __shared__ float sWb[TS];                           // the swept candidates' bias (forward, dh)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const int d = a.d;
   const bool vec = a.vec != 0;
@@ -127,6 +139,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
     }
     z0 += __shfl_xor(z0, 16, 64);
     z0 += __shfl_xor(z0, 32, 64);
+    if (a.bias && sid) z0 += a.bias[sid];
   } else if (MODE == DH && sid) {
     slse = a.lse[si];
     z0 = a.z0[si];
@@ -155,6 +168,9 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
   };
   if (w_begin < w_end) tile_ids(w_begin);
   float m = NEG, s = 0.f;
+  // dEc with a bias: the stationary candidate's bias, and this lane's sum of p over the rows it met
+  const float sbias = MODE == DEC && a.bias && sid ? a.bias[sid] : 0.f;
+  float psum = 0.f;
   f32x4 O[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) O[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -175,6 +191,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
       }
       sWid[tid] = id;
       sWlse[tid] = l;
+      if (MODE != DEC && a.bias) sWb[tid] = id ? a.bias[id] : 0.f;
     }
     Frag<T> fr[NCH];
 #pragma unroll
@@ -203,6 +220,10 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
           frag_load_vec(A, &W[(sub * 16 + c) * LDW + kk * 32 + 8 * g]);
           acc = mma(A, S[kk], acc);                   // acc[r] = z[swept sub * 16 + 4 g + r][stationary c]
         }
+        if (a.bias) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[r] += MODE == DEC ? sbias : sWb[sub * 16 + 4 * g + r];
+        }
         bool lv[4];
         float zm = NEG;
 #pragma unroll
@@ -215,7 +236,9 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
             if (lv[r]) zm = fmaxf(zm, acc[r]);
           } else {
             const float l = MODE == DEC ? sWlse[wi] : slse;
-            frag_set(Pf, h * 4 + r, lv[r] ? expf(acc[r] - l) : 0.f);
+            const float p = lv[r] ? expf(acc[r] - l) : 0.f;
+            frag_set(Pf, h * 4 + r, p);
+            if (MODE == DEC) psum += p;
           }
         }
         if (MODE == FWD && zm > NEG) {
@@ -292,6 +315,12 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
     }
     return;
   }
+  if (a.dbslab) {                                     // uniform: the four lane groups' sums of candidate c, in order
+    psum += __shfl_xor(psum, 16, 64);
+    psum += __shfl_xor(psum, 32, 64);
+    const int64_t j = s0 + wave * 16 + c;
+    if (g == 0 && j < a.K) a.dbslab[(int64_t)blockIdx.y * a.K + j] = scale * psum;
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t j = s0 + wave * 16 + 4 * g + r;
@@ -343,6 +372,7 @@ __global__ __launch_bounds__(256) void generic_kernel(Args a) {
       if (k < d) z0 = __builtin_fmaf(sv[i], to_f(prow[k]), z0);
     }
     z0 = wave_sum(z0);
+    if (a.bias) z0 += a.bias[sid];
   } else if (MODE == DH && sid) {
     slse = a.lse[si];
     z0 = a.z0[si];
@@ -356,7 +386,7 @@ __global__ __launch_bounds__(256) void generic_kernel(Args a) {
     w_begin = (int64_t)blockIdx.y * per;
     w_end = min(a.K, w_begin + per);
   }
-  float m = NEG, s = 0.f;
+  float m = NEG, s = 0.f, psum = 0.f;
   for (int64_t wi = w_begin + wave; wi < w_end; wi += 4) {
     const int32_t wid = MODE == DEC ? row_id(wi) : cand_id(wi);
     const int32_t cid = MODE == DEC ? sid : wid, rid = MODE == DEC ? wid : sid;
@@ -370,12 +400,14 @@ __global__ __launch_bounds__(256) void generic_kernel(Args a) {
       z = __builtin_fmaf(sv[i], wv[i], z);
     }
     z = wave_sum(z);
+    if (a.bias) z += a.bias[cid];
     if (MODE == FWD) {
       const float mn = fmaxf(m, z);
       s = s * expf(m - mn) + expf(z - mn);
       m = mn;
     } else {
       const float p = expf(z - (MODE == DEC ? a.lse[wi] : slse));
+      psum += p;
 #pragma unroll
       for (int i = 0; i < GEN_C; ++i) acc[i] = __builtin_fmaf(p, wv[i], acc[i]);
     }
@@ -405,9 +437,12 @@ __global__ __launch_bounds__(256) void generic_kernel(Args a) {
     const int k = lane + 64 * i;
     if (k < d) red[wave * d + k] = acc[i];
   }
+  if (lane == 0) rm[wave] = psum;
   __syncthreads();
   const float scale = (a.dloss ? *a.dloss : 1.f) / *a.div;
   const bool first = blockIdx.y == 0;
+  if (MODE == DEC && a.dbslab && tid == 0)
+    a.dbslab[(int64_t)blockIdx.y * a.K + si] = scale * (((rm[0] + rm[1]) + rm[2]) + rm[3]);
   const float cf = MODE == DH && sid && first ? (expf(z0 - slse) - 1.f) * scale : 0.f;
   if (MODE == DH && first && tid == 0) a.coef[si] = cf;
   for (int col = tid; col < d; col += 256) {
@@ -565,11 +600,18 @@ static bool supported(int dtype, int64_t d, int64_t K) {
 
 static bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
+// the rs_sce_head_* entries: bf16 rows up to WIDE_DMAX take the MFMA sweep (DP = 256)
+constexpr int64_t WIDE_DMAX = 256;
+
+static bool on_sweep(int dtype, int64_t d, bool wide) {
+  return d <= 128 || (wide && dtype == RS_DTYPE_BF16 && d <= WIDE_DMAX);
+}
+
 // items: the stationary items (rows or candidates); ysplits: the splits of the swept side
 template <int MODE>
-static void launch(int dtype, int64_t d, int64_t items, int ysplits, hipStream_t s, const Args& a) {
+static void launch(int dtype, int64_t d, int64_t items, int ysplits, hipStream_t s, const Args& a, bool wide) {
   const bool bf = dtype == RS_DTYPE_BF16;
-  if (d > 128) {                                     // one workgroup per item
+  if (!on_sweep(dtype, d, wide)) {                   // one workgroup per item
     const dim3 grid((unsigned)items, (unsigned)ysplits);
     if (bf) hipLaunchKernelGGL((generic_kernel<__bf16, MODE>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((generic_kernel<float, MODE>), grid, dim3(256), 0, s, a);
@@ -578,11 +620,80 @@ static void launch(int dtype, int64_t d, int64_t items, int ysplits, hipStream_t
   const dim3 grid((unsigned)cdiv(items, (int64_t)TS), (unsigned)ysplits);
   if (bf) {
     if (d <= 64) hipLaunchKernelGGL((sweep_kernel<__bf16, 64, MODE>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((sweep_kernel<__bf16, 128, MODE>), grid, dim3(256), 0, s, a);
+    else if (d <= 128) hipLaunchKernelGGL((sweep_kernel<__bf16, 128, MODE>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((sweep_kernel<__bf16, 256, MODE>), grid, dim3(256), 0, s, a);
   } else {
     if (d <= 64) hipLaunchKernelGGL((sweep_kernel<float, 64, MODE>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((sweep_kernel<float, 128, MODE>), grid, dim3(256), 0, s, a);
   }
+}
+
+static int fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab, const int32_t* count,
+               const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K, const float* divisor,
+               void* ws, float* out, void* stream, bool wide) {
+  if (!supported(dtype, d, K)) return RS_ERR_UNSUPPORTED;
+  if (cap <= 0 || cap >= ((int64_t)1 << 31) || V1 < 1 || V1 >= ((int64_t)1 << 31) || !hl || !lab || !E || !cand ||
+      !divisor || !ws || !out || ldh < d || !al16(ws))
+    return RS_ERR_ARG;
+  const int64_t sz = dtype == RS_DTYPE_BF16 ? 2 : 4;
+  Args a = {};
+  a.hl = hl; a.ldh = ldh; a.lab = lab; a.cnt = count; a.cap = cap; a.E = E; a.V1 = V1; a.cand = cand; a.K = K;
+  a.d = (int)d;
+  a.bias = bias;
+  a.vec = al16(hl) && al16(E) && (ldh * sz) % 16 == 0 && (d * sz) % 16 == 0;
+  const WsLayout L = ws_layout(cap, K, d);
+  a.lse = (float*)ws;
+  a.z0 = a.lse + cap;
+  a.pm = a.lse + L.pm;
+  a.ps = a.lse + L.ps;
+  double* part = (double*)(a.lse + L.part);
+  hipStream_t s = (hipStream_t)stream;
+  launch<FWD>(dtype, d, cap, L.ks, s, a, wide);
+  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)L.nb), dim3(256), 0, s, a.pm, a.ps, L.ks, lab, count, cap, V1,
+                     a.z0, a.lse, part);
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, part, L.nb, divisor, out);
+  return (int)hipGetLastError();
+}
+
+static int bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab, const int32_t* count,
+               const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K, const float* divisor,
+               const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc, float* dbc, int64_t* keys,
+               void* stream, bool wide) {
+  if (!supported(dtype, d, K)) return RS_ERR_UNSUPPORTED;
+  if (cap <= 0 || cap >= ((int64_t)1 << 31) || V1 < 1 || V1 >= ((int64_t)1 << 31) || !hl || !lab || !E || !cand ||
+      !divisor || !ws || !dh || !coef || !pg || !dEc || ldh < d || !al16(ws))
+    return RS_ERR_ARG;
+  const int64_t sz = dtype == RS_DTYPE_BF16 ? 2 : 4;
+  Args a = {};
+  a.hl = hl; a.ldh = ldh; a.lab = lab; a.cnt = count; a.cap = cap; a.E = E; a.V1 = V1; a.cand = cand; a.K = K;
+  a.d = (int)d;
+  a.bias = bias;
+  a.vec = al16(hl) && al16(E) && (ldh * sz) % 16 == 0 && (d * sz) % 16 == 0;
+  a.lse = (float*)ws;
+  a.z0 = a.lse + cap;
+  a.div = divisor; a.dloss = dloss; a.dh = dh; a.coef = coef; a.pg = pg;
+  const WsLayout L = ws_layout(cap, K, d);
+  const int sp = splits_of(cap, K, &a.rows_per_split);
+  a.slab = sp > 1 ? a.lse + L.slab : dEc;
+  if (bias) a.dbslab = sp > 1 ? a.lse + (L.total + 3) / 4 * 4 : dbc;
+  hipStream_t s = (hipStream_t)stream;
+  launch<DH>(dtype, d, cap, L.ks, s, a, wide);
+  launch<DEC>(dtype, d, K, sp, s, a, wide);
+  if (sp > 1) {
+    hipError_t e = launch_reduce_slabs(a.slab, sp, K * d, K * d, dEc, nullptr, 0, s);
+    if (e != hipSuccess) return (int)e;
+    if (bias && (e = launch_reduce_slabs(a.dbslab, sp, K, K, dbc, nullptr, 0, s)) != hipSuccess) return (int)e;
+  }
+  if (keys)
+    hipLaunchKernelGGL(keys_kernel, dim3((unsigned)cdiv(cap + K, (int64_t)256)), dim3(256), 0, s, lab, count, cap,
+                       cand, K, V1, keys);
+  return (int)hipGetLastError();
+}
+
+// the rs_sce_head_* workspace, in floats: the layout above, then the dbc row-split slabs [sp][K] (with a bias)
+static int64_t head_ws_total(int64_t cap, int64_t K, int64_t d, bool has_bias) {
+  const WsLayout L = ws_layout(cap, K, d);
+  return has_bias && L.sp > 1 ? (L.total + 3) / 4 * 4 + (int64_t)L.sp * K : L.total;
 }
 
 }  // namespace sce
@@ -604,59 +715,45 @@ int64_t rs_sas_sce_dh_splits(int64_t cap, int64_t K, int64_t d) {
 int rs_sas_sce_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
                    const int32_t* count, const void* E, int64_t V1, const int64_t* cand, int64_t K,
                    const float* divisor, void* ws, float* out, void* stream) {
-  if (!sce::supported(dtype, d, K)) return RS_ERR_UNSUPPORTED;
-  if (cap <= 0 || cap >= ((int64_t)1 << 31) || V1 < 1 || V1 >= ((int64_t)1 << 31) || !hl || !lab || !E || !cand ||
-      !divisor || !ws || !out || ldh < d || !sce::al16(ws))
-    return RS_ERR_ARG;
-  const int64_t sz = dtype == RS_DTYPE_BF16 ? 2 : 4;
-  sce::Args a = {};
-  a.hl = hl; a.ldh = ldh; a.lab = lab; a.cnt = count; a.cap = cap; a.E = E; a.V1 = V1; a.cand = cand; a.K = K;
-  a.d = (int)d;
-  a.vec = sce::al16(hl) && sce::al16(E) && (ldh * sz) % 16 == 0 && (d * sz) % 16 == 0;
-  const sce::WsLayout L = sce::ws_layout(cap, K, d);
-  a.lse = (float*)ws;
-  a.z0 = a.lse + cap;
-  a.pm = a.lse + L.pm;
-  a.ps = a.lse + L.ps;
-  double* part = (double*)(a.lse + L.part);
-  hipStream_t s = (hipStream_t)stream;
-  sce::launch<sce::FWD>(dtype, d, cap, L.ks, s, a);
-  hipLaunchKernelGGL(sce::combine_kernel, dim3((unsigned)L.nb), dim3(256), 0, s, a.pm, a.ps, L.ks, lab, count, cap, V1,
-                     a.z0, a.lse, part);
-  hipLaunchKernelGGL(sce::finish_kernel, dim3(1), dim3(256), 0, s, part, L.nb, divisor, out);
-  return (int)hipGetLastError();
+  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, nullptr, V1, cand, K, divisor, ws, out, stream, false);
 }
 
 int rs_sas_sce_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
                    const int32_t* count, const void* E, int64_t V1, const int64_t* cand, int64_t K,
                    const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
                    int64_t* keys, void* stream) {
-  if (!sce::supported(dtype, d, K)) return RS_ERR_UNSUPPORTED;
-  if (cap <= 0 || cap >= ((int64_t)1 << 31) || V1 < 1 || V1 >= ((int64_t)1 << 31) || !hl || !lab || !E || !cand ||
-      !divisor || !ws || !dh || !coef || !pg || !dEc || ldh < d || !sce::al16(ws))
-    return RS_ERR_ARG;
-  const int64_t sz = dtype == RS_DTYPE_BF16 ? 2 : 4;
-  sce::Args a = {};
-  a.hl = hl; a.ldh = ldh; a.lab = lab; a.cnt = count; a.cap = cap; a.E = E; a.V1 = V1; a.cand = cand; a.K = K;
-  a.d = (int)d;
-  a.vec = sce::al16(hl) && sce::al16(E) && (ldh * sz) % 16 == 0 && (d * sz) % 16 == 0;
-  a.lse = (float*)ws;
-  a.z0 = a.lse + cap;
-  a.div = divisor; a.dloss = dloss; a.dh = dh; a.coef = coef; a.pg = pg;
-  const sce::WsLayout L = sce::ws_layout(cap, K, d);
-  const int sp = sce::splits_of(cap, K, &a.rows_per_split);
-  a.slab = sp > 1 ? a.lse + L.slab : dEc;
-  hipStream_t s = (hipStream_t)stream;
-  sce::launch<sce::DH>(dtype, d, cap, L.ks, s, a);
-  sce::launch<sce::DEC>(dtype, d, K, sp, s, a);
-  if (sp > 1) {
-    hipError_t e = launch_reduce_slabs(a.slab, sp, K * d, K * d, dEc, nullptr, 0, s);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (keys)
-    hipLaunchKernelGGL(sce::keys_kernel, dim3((unsigned)cdiv(cap + K, (int64_t)256)), dim3(256), 0, s, lab, count, cap,
-                       cand, K, V1, keys);
-  return (int)hipGetLastError();
+  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, nullptr, V1, cand, K, divisor, dloss, ws, dh, coef, pg, dEc,
+                  nullptr, keys, stream, false);
+}
+
+int64_t rs_sce_head_ws_bytes(int dtype, int64_t cap, int64_t K, int64_t d, int has_bias) {
+  if (cap <= 0 || K <= 0 || !sce::supported(dtype, d, K)) return -1;
+  return 4 * sce::head_ws_total(cap, K, d, has_bias != 0);
+}
+
+int64_t rs_sce_head_dh_splits(int dtype, int64_t cap, int64_t K, int64_t d) {
+  if (cap <= 0 || K <= 0 || !sce::supported(dtype, d, K)) return -1;
+  return sce::ksplits_of(cap, K, d);
+}
+
+int rs_sce_head_path(int dtype, int64_t d) {
+  if (!sce::supported(dtype, d, 1)) return -1;
+  return sce::on_sweep(dtype, d, true) ? 1 : 0;
+}
+
+int rs_sce_head_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                    const int32_t* count, const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K,
+                    const float* divisor, void* ws, float* out, void* stream) {
+  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, bias, V1, cand, K, divisor, ws, out, stream, true);
+}
+
+int rs_sce_head_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                    const int32_t* count, const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K,
+                    const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
+                    float* dbc, int64_t* keys, void* stream) {
+  if (!bias != !dbc) return sce::supported(dtype, d, K) ? RS_ERR_ARG : RS_ERR_UNSUPPORTED;
+  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, bias, V1, cand, K, divisor, dloss, ws, dh, coef, pg, dEc, dbc,
+                  keys, stream, true);
 }
 
 int rs_uniform_items(const uint64_t* seed_base, uint64_t salt, int64_t item_num, int64_t K, int64_t* out, void* stream) {

@@ -107,9 +107,16 @@ class DeviceWarpSampler:
 class DeviceBertMasker:
     n_outputs = 2
 
-    def __init__(self, u2seq, num_items, batch_size, max_len, mask_prob, device="cuda", seed=None):
+    def __init__(self, u2seq, num_items, batch_size, max_len, mask_prob, device="cuda", seed=None, shared_negs=None):
         """u2seq: list (per user) of training item-id lists (the reference's ``train`` dict values in user
-        order).  The [MASK] token is num_items + 1, as BERTEmbedding's table (V+2 rows) expects."""
+        order).  The [MASK] token is num_items + 1, as BERTEmbedding's table (V+2 rows) expects.
+        shared_negs=K: batches are (tokens, labels, cand) with cand int64 (K,) drawn uniformly with replacement from
+        [1, num_items] on the device (rs_uniform_items on the step seed rs_bert_mask advanced, its own salt) -- the
+        candidates of the sampled-softmax loss, shared by the whole batch."""
+        self.shared_negs = None if shared_negs is None else int(shared_negs)
+        if self.shared_negs is not None and self.shared_negs < 1:
+            raise ValueError("shared_negs must be a positive number of candidates")
+        self.n_outputs = 2 if self.shared_negs is None else 3
         self.device = torch.device(device)
         self.offsets, self.items, self.n_users = _flatten(u2seq, self.device)
         self.num_items = int(num_items)
@@ -123,6 +130,8 @@ class DeviceBertMasker:
             g.manual_seed(seed)
             self.gen.manual_seed(seed)
         self.salt = int(torch.randint(0, 2 ** 62, (1,), generator=g).item())
+        if self.shared_negs is not None:
+            self.cand_salt = int(torch.randint(0, 2 ** 62, (1,), generator=g).item())
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)   # {step seed, cursor}
         self.perm = torch.arange(self.n_users, dtype=torch.int64, device=self.device)
         self.cnt = 0
@@ -132,13 +141,31 @@ class DeviceBertMasker:
         torch.randperm(self.n_users, generator=self.gen, device=self.device, out=self.perm)
         self.state[1:2].zero_()
 
-    def sample_into(self, tokens, labels, draws=None):
+    def sample_into(self, tokens, labels, *rest, draws=None):
+        """Write the next batch into existing (batch_size, max_len) int64 device tensors (draws, also accepted as the
+        last positional argument: see ops.bert_mask).  With shared_negs=K the third tensor is cand, int64 (K,)."""
+        cand = None
+        if self.shared_negs is not None:
+            if not rest:
+                raise ValueError(f"shared_negs={self.shared_negs}: sample_into needs cand")
+            cand, rest = rest[0], rest[1:]
+            if cand.shape != (self.shared_negs,) or cand.dtype != torch.int64 or not cand.is_contiguous():
+                raise ValueError(f"cand must be a contiguous int64 tensor of shape ({self.shared_negs},)")
+        if len(rest) > 1 or (rest and draws is not None):
+            raise TypeError("sample_into takes (tokens, labels[, cand][, draws])")
+        draws = rest[0] if rest else draws
         ops.bert_mask(self.offsets, self.items, self.n_users, self.num_items, self.mask_prob, self.perm, self.state,
                       self.salt, tokens, labels, draws)
+        if cand is not None:
+            ops.uniform_items(self.state[0:1], self.cand_salt, self.num_items, cand)   # the seed just advanced
 
     def sample(self):
         shape = (self.batch_size, self.max_len)
         tokens, labels = (torch.empty(shape, dtype=torch.int64, device=self.device) for _ in range(2))
+        if self.shared_negs is not None:
+            cand = torch.empty(self.shared_negs, dtype=torch.int64, device=self.device)
+            self.sample_into(tokens, labels, cand)
+            return tokens, labels, cand
         self.sample_into(tokens, labels)
         return tokens, labels
 

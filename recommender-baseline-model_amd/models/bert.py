@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from ..engine_util import as_ids, compute_dtype, require_cuda
 from .base import BaseModel
-from .bert_model.bert import BERT, BERTEngine, _BERTFunction, build_flat
+from .bert_model.bert import BERT, BERTEngine, _BERTFunction, _BERTSCEFunction, build_flat
 
 
 class BERTModel(BaseModel):
@@ -69,6 +69,27 @@ class BERTModel(BaseModel):
         """int32 (B,) rank of target[b] among all items (0 = first), x's own items left out when exclude_seen."""
         dev = self._flat.device
         return self.engine().full_rank(as_ids(x, dev), as_ids(target, dev).reshape(-1), exclude_seen)
+
+    def sampled_ce_loss(self, tokens, labels, cand):
+        """Scalar loss of the sampled softmax over batch-shared candidates (differentiable; available whatever
+        bert_loss says).  cand: int64 (K,), shared by every position; with E = out.weight, b = out.bias:
+
+            h_r   = BERT(tokens)[r]                            for every position r with labels_r != 0 ("labelled")
+            z_r0  = <h_r, E[labels_r]> + b[labels_r]
+            z_rj  = <h_r, E[cand_j]> + b[cand_j],  j = 1..K
+            live(r, j) = cand_j != 0 and cand_j != labels_r    id 0 = an ignored slot; accidental hits masked
+            loss  = (1 / max(n, 1)) * sum_r [ log(exp(z_r0) + sum_{live j} exp(z_rj)) - z_r0 ],   n = #labelled
+
+        Duplicate candidates count separately; an id outside out.weight's rows counts as 0; there is no logQ
+        correction (a log-probability added to the bias is the hook for one).  With cand = every item it is the
+        reference's cross-entropy up to class 0, which that loss counts and no candidate list can name.  A row with
+        no live candidate, and a batch with no labelled row, give loss 0 and zero gradients; rows of out.weight /
+        out.bias outside the batch's labels and candidates get none.  Call backward() before the next loss call."""
+        eng = self.engine()
+        dev = self._flat.device
+        ids, lab, cand = as_ids(tokens, dev), as_ids(labels, dev), as_ids(cand, dev)
+        params = [p for _, p in self.named_parameters()]
+        return _BERTSCEFunction.apply(eng, ids, lab, cand, self.training, *params)
 
     def forward(self, x):
         eng = self.engine()

@@ -20,6 +20,12 @@ training loss (BS/trainers/bert.py:30-41): CE(ignore_index=0) only needs the
 labelled rows, so the fused step compacts them on the device (rs_compact_rows /
 rs_gather_rows), runs the vocabulary GEMM + CE on those rows only, and scatters
 the hidden-state gradient back (rs_scatter_rows).
+
+bert_loss="sampled_ce" (sce_forward / sce_backward): the same compaction, then the softmax over the positive and K
+candidates shared by the whole batch instead of the whole vocabulary (sas_sce.hip, rs_sce_head_fwd / _bwd with
+E = out.weight and bias = out.bias): cost and memory follow K, no buffer is shaped by V.  The head's part of
+out.weight's / out.bias's gradient touches at most cap + K rows and goes through an inverted index over those keys
+(rs_item_index_build, rs_item_grad_f32) on the side stream, beside the encoder's backward.
 """
 import math
 import os
@@ -34,6 +40,14 @@ from ...engine_util import Workspace, as_ids, capture_event, compute_dtype, requ
 from ...flat import ALIGN, FlatParams
 
 LN_EPS = 1e-6  # utils/layer_norm.py:8
+BERT_LOSSES = ("ce", "sampled_ce")
+SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
+
+
+def _check_shared_negs(K):
+    kmax = ops.sas_sce_max_k()
+    if K < 1 or K > kmax:
+        raise ValueError(f"the sampled-softmax head takes 1 .. {kmax} shared candidates, got {K}")
 
 
 # ---------------------------------------------------------------- parameter containers (reference layout)
@@ -109,6 +123,16 @@ class BERT(nn.Module):
         self.num_blocks = args.bert_num_blocks
         self.dropout = float(args.bert_dropout)
         self.hidden_dropout = float(args.bert_hidden_dropout)
+        # the training objective FusedTrainStep takes by default: "ce" (the reference's cross-entropy over the whole
+        # vocabulary) or "sampled_ce" (the softmax over the label and bert_shared_negs candidates shared by the batch)
+        self.bert_loss = str(getattr(args, "bert_loss", None) or "ce")
+        if self.bert_loss not in BERT_LOSSES:
+            raise ValueError(f"bert_loss must be one of {BERT_LOSSES}, got {self.bert_loss!r}")
+        self.bert_shared_negs = int(getattr(args, "bert_shared_negs", 0) or 0)
+        if self.bert_loss == "sampled_ce":
+            if getattr(args, "bert_shared_negs", None) is None:
+                raise ValueError("bert_loss='sampled_ce' needs args.bert_shared_negs = K (the shared candidates)")
+            _check_shared_negs(self.bert_shared_negs)
         vocab_size = args.num_items + 2          # [MASK] = num_items + 1, padding = 0
         self.embedding = BERTEmbedding(vocab_size=vocab_size, embed_size=self.hidden, max_len=self.max_len)
         self.transformer_blocks = nn.ModuleList(
@@ -156,6 +180,8 @@ class BERTEngine:
         self.V1p = -(-self.V1 // 64) * 64
         self.dt = model.cdtype
         self.dev = flat.device
+        # the objective of the fused step (FusedTrainStep sets it): decides the head's gradient contract
+        self.loss = b.bert_loss
         if self.dt == torch.bfloat16:
             flat.enable_bf16()
         self.ws = Workspace(self.dev)
@@ -402,8 +428,9 @@ class BERTEngine:
         bias column sums with accumulate off; rows without labelled logits get exact zeros) and nothing else
         accumulates into it -- a head variant that accumulated would double-count the previous step's gradient
         (tests/test_bert.py ...overwritten_head_grads_match_zeroed, tests/test_dp_gpu.py
-        ...unzeroed_head_grads_equal_zeroed under the in-place all-reduce)."""
-        if self.V1 * self.d < (1 << 24):
+        ...unzeroed_head_grads_equal_zeroed under the in-place all-reduce).  The sampled-softmax head is such a
+        variant: it ACCUMULATES at most cap + K rows into a zeroed range, so under it there is no such range."""
+        if self.loss == "sampled_ce" or self.V1 * self.d < (1 << 24):
             return None
         return self.head_grad_range()
 
@@ -637,6 +664,96 @@ class BERTEngine:
         self.encode_backward(s, dxL, grad)
 
 
+    # ---- sampled softmax over batch-shared candidates (sas_sce.hip, rs_sce_head_*) -----------------
+    def sce_forward(self, tokens, labels, cand, training, loss_out, max_labelled=None, clone_seed=True):
+        """Encoder forward, then on the labelled rows only the softmax cross-entropy of the label against the K
+        candidates `cand` (int64 [K], shared by every row; id 0 and a row's own label are masked;
+        BERTModel.sampled_ce_loss has the definition) with E = out.weight, bias = out.bias.  loss_out = {loss sum,
+        labelled count, mean}; the divisor is max(count, 1).  Returns the saved state for sce_backward.  The sce_*
+        buffers are sized by (cap, K, d) alone; nothing here allocates per step or reads the host."""
+        d, dt = self.d, self.dt
+        if dt == torch.bfloat16 and d % 8:
+            raise ValueError(f"the bf16 sampled-softmax head needs hidden units divisible by 8 (got {d}); "
+                             "use fp32 mode (rs_dtype='fp32') at this width")
+        if ops.sce_head_path(d, dt) < 0:
+            raise ValueError(f"the sampled-softmax head covers hidden units up to 1024 (got {d})")
+        cand = cand.reshape(-1).contiguous()
+        K = cand.numel()
+        _check_shared_negs(K)
+        # the token index on the side stream, after the first forward launch (train_loss_and_backward has the why)
+        side_box = {}
+        if self._det_table():
+            fork = capture_event()
+            fork.record()
+            side_box["fork"] = fork
+
+        def after_first():
+            if "fork" in side_box:
+                side_box["side"] = self._token_index(tokens, after=side_box["fork"])
+        xL, s = self.encode(tokens, training, clone_seed=clone_seed, after_first=after_first)
+        if side_box.get("side") is not None:
+            s["side"] = side_box["side"]
+        B, T = tokens.shape
+        M = B * T
+        g = self.ws.get
+        cap = int(max_labelled or M)
+        idx, rank, cnt = g("cidx", (cap,), torch.int32), g("crank", (M,), torch.int32), g("ccount", (1,), torch.int32)
+        ops.compact_rows(labels, cap, idx, rank, cnt)
+        hl, lab = g("hl", (cap, d), dt), g("lab", (cap,), torch.int64)
+        ops.gather_rows(xL, idx, cnt, cap, hl, labels, lab)
+        div = g("sce_div", (1,), torch.float32)
+        div.copy_(cnt)
+        div.clamp_(min=1.0)                       # an all-unlabelled batch: loss 0, zero gradients
+        ws = g("sce_ws", (ops.sce_head_ws_numel(cap, K, d, dt),), torch.float32)
+        ops.sce_head_fwd(hl, lab, cnt, cap, self.W("out.weight"), self.Wf("out.bias"), cand, div, ws, loss_out)
+        s.update(sce=dict(cap=cap, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, ws=ws, cand=cand))
+        return s
+
+    def sce_backward(self, s, grad, dloss=None):
+        """Accumulates every parameter gradient of sce_forward's loss (times *dloss, a device scalar, if given) into
+        the flat fp32 buffer ``grad``, whose out.weight / out.bias range must be zero: the head adds coef_r h_r at row
+        lab_r and dEc[j] at row cand_j of out.weight, coef_r and dbc[j] at those elements of out.bias -- through one
+        inverted index over the cap + K keys (rs_item_index_build; rs_item_grad_f32 over {pg, dEc}, then at d = 1 over
+        {coef, dbc}: one writer per element, duplicates summed in sorted-entry order, no float atomics).  Those three
+        launches depend on the head alone and run on the side stream beside the encoder's backward, forked after the
+        main stream's next launch is issued (a captured graph keeps a node's first child on its queue) and joined
+        at the end."""
+        c = s["sce"]
+        d, dt = self.d, self.dt
+        f32 = torch.float32
+        g = self.ws.get
+        cap, cnt, hl, lab, cand = c["cap"], c["cnt"], c["hl"], c["lab"], c["cand"]
+        K = cand.numel()
+        M = s["B"] * s["T"]
+        GW, Gb = self.flat.view("out.weight", grad), self.flat.view("out.bias", grad)
+        sk = ops.sce_head_dh_splits(cap, K, d, dt)          # one fp32 slab per split of the candidates
+        dh = g("sce_dh", (sk, cap, d), f32)
+        src, bsrc = g("sce_src", (cap + K, d), f32), g("sce_bsrc", (cap + K,), f32)
+        keys = g("sce_keys", (cap + K,), torch.int64)
+        ops.sce_head_bwd(hl, lab, cnt, cap, self.W("out.weight"), self.Wf("out.bias"), cand, c["div"], dloss, c["ws"],
+                         dh, bsrc[:cap], src[:cap], src[cap:], bsrc[cap:], keys)
+        # the index's key range: past the counting sort's table limit, so that the radix path is taken, the workspace
+        # is sized by the entry count alone and the sorted index does not depend on the source width
+        rows = max(self.V1, SCE_INDEX_ROWS)
+        iws = g("sce_itemidx", (ops.item_index_ws_bytes(1, cap + K, rows, d),), torch.uint8)
+        cur = torch.cuda.current_stream()
+        ev = capture_event()
+        ev.record(cur)
+        dxL = self._buf((M, d))
+        ops.splitk_scatter_rows(dh, sk, cap, c["rank"], dxL)
+        if getattr(self, "_side", None) is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+        self._side.wait_event(ev)
+        with torch.cuda.stream(self._side):
+            ops.item_index_build([keys], rows, d, iws)
+            ops.item_grad(iws, 1, cap + K, src, 1.0, 0.0, 0, s["sb"], None, None, None, GW, table_rows=rows)
+            ops.item_grad(iws, 1, cap + K, bsrc.view(cap + K, 1), 1.0, 0.0, 0, s["sb"], None, None, None,
+                          Gb.view(-1, 1), table_rows=rows)
+            join = capture_event()
+            join.record(self._side)
+        self.encode_backward(s, dxL, grad)
+        cur.wait_event(join)
+
     def _sharded_head_and_backward(self, s, xL, hl, lab, idx, rank, cnt, labels, cap, loss_out, grad, split):
         """The vocabulary head with out.weight / out.bias sharded over the data-parallel ranks (vocab_parallel.py):
         loss_out = (loss sum, labelled count, mean) of the GLOBAL batch on every rank; gradients are those of the
@@ -715,6 +832,24 @@ class _BERTFunction(torch.autograd.Function):
         return (None, None, None, *[eng.flat.view(n, grad) for n in eng.flat.names_in_module_order])
 
 
+class _BERTSCEFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, ids, labels, cand, training, *params):
+        engine.sync_compute_weights()
+        out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
+        ctx.saved = engine.sce_forward(ids, labels, cand, training, out)
+        ctx.engine = engine
+        return out[2].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        eng = ctx.engine
+        grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
+        eng.sce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
+        ctx.saved = None
+        return (None, None, None, None, None, *[eng.flat.view(n, grad) for n in eng.flat.names_in_module_order])
+
+
 def build_flat(model, device):
     flat = FlatParams(model, device, order=_storage_order)
     flat.names_in_module_order = [n for n, _ in model.named_parameters()]
@@ -727,4 +862,4 @@ def require(model):
     return p.device
 
 
-__all__ = ["BERT", "BERTEngine", "_BERTFunction", "build_flat", "as_ids", "compute_dtype", "require"]
+__all__ = ["BERT", "BERTEngine", "_BERTFunction", "_BERTSCEFunction", "build_flat", "as_ids", "compute_dtype", "require"]

@@ -910,6 +910,57 @@ def sas_sce_bwd(hl, lab, count, cap, E, cand, divisor, dloss, ws, dh, coef, pg, 
          K, ptr(divisor), ptr(dloss), ptr(ws), ptr(dh), ptr(coef), ptr(pg), ptr(dEc), ptr(keys), stream())
 
 
+# ---- the sampled-softmax head for an untied output layer with a bias (sas_sce.hip: rs_sce_head_*) -----------
+def sce_head_path(d, dtype):
+    """1: the MFMA sweep (fp32 d <= 128, bf16 d <= 256), 0: the plain kernel, < 0: unsupported (host only)."""
+    return int(_lib.lib().rs_sce_head_path(_lib.BF16 if dtype == torch.bfloat16 else
+                                           (_lib.F32 if dtype == torch.float32 else -1), d))
+
+
+def sce_head_ws_numel(cap, K, d, dtype, has_bias=True):
+    """fp32 elements of the head's workspace: a function of (dtype, cap, K, d, bias or not) alone (host only)."""
+    n = int(_lib.lib().rs_sce_head_ws_bytes(_lib.BF16 if dtype == torch.bfloat16 else _lib.F32, cap, K, d,
+                                            int(has_bias)))
+    if n < 0:
+        raise RuntimeError("rs_sce_head_ws_bytes: bad arguments")
+    return n // 4
+
+
+def sce_head_dh_splits(cap, K, d, dtype):
+    """Slabs rs_sce_head_bwd writes dh in (one per split of the candidates; host only)."""
+    return int(_lib.lib().rs_sce_head_dh_splits(_lib.BF16 if dtype == torch.bfloat16 else _lib.F32, cap, K, d))
+
+
+def _sce_head_bias(bias, E):
+    assert bias is None or (bias.dtype == torch.float32 and bias.shape == (E.shape[0],) and bias.is_contiguous())
+
+
+def sce_head_fwd(hl, lab, count, cap, E, bias, cand, divisor, ws, out):
+    """sas_sce_fwd on the logits <h, E[.]> + bias[.] (bias fp32 [V1] or None): rs_sce_head_fwd."""
+    d, K = hl.shape[1], cand.numel()
+    assert hl.shape[0] >= cap and lab.numel() >= cap and E.dtype == hl.dtype and E.shape[1] == d and E.is_contiguous()
+    assert cand.dtype == torch.int64 and cand.is_contiguous()
+    assert ws.numel() >= sce_head_ws_numel(cap, K, d, hl.dtype, bias is not None)
+    _sce_head_bias(bias, E)
+    call("rs_sce_head_fwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), ptr(bias),
+         E.shape[0], ptr(cand), K, ptr(divisor), ptr(ws), ptr(out), stream())
+
+
+def sce_head_bwd(hl, lab, count, cap, E, bias, cand, divisor, dloss, ws, dh, coef, pg, dEc, dbc, keys=None):
+    """sas_sce_bwd's outputs on those logits, and dbc fp32 [K] (with a bias; None without): rs_sce_head_bwd."""
+    d, K = hl.shape[1], cand.numel()
+    assert dh.numel() >= sce_head_dh_splits(cap, K, d, hl.dtype) * cap * d and coef.numel() >= cap
+    assert pg.numel() >= cap * d and dEc.numel() >= K * d
+    assert keys is None or (keys.numel() >= cap + K and keys.dtype == torch.int64)
+    assert ws.numel() >= sce_head_ws_numel(cap, K, d, hl.dtype, bias is not None)
+    assert E.shape[1] == d and E.is_contiguous() and E.dtype == hl.dtype
+    _sce_head_bias(bias, E)
+    assert (dbc is None) == (bias is None) and (dbc is None or (dbc.dtype == torch.float32 and dbc.numel() >= K))
+    call("rs_sce_head_bwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), ptr(bias),
+         E.shape[0], ptr(cand), K, ptr(divisor), ptr(dloss), ptr(ws), ptr(dh), ptr(coef), ptr(pg), ptr(dEc), ptr(dbc),
+         ptr(keys), stream())
+
+
 def uniform_items(seed_base, salt, item_num, out):
     """out (int64, device): uniform draws with replacement over [1, item_num] from (seed_base, salt)."""
     call("rs_uniform_items", ptr(seed_base), salt, item_num, out.numel(), ptr(out), stream())

@@ -168,6 +168,10 @@ class FusedTrainStep:
         "ce" the batch's neg plays no part and may be None; single device only.  "sampled_ce": the same softmax over
         the positive and K candidates shared by the whole batch (SASModel.sampled_ce_loss); the batch is (seq, pos,
         cand) with cand int64 (K,); single device, steps_per_graph = 1.
+        loss (BERT): None = the model's args.bert_loss (the reference's cross-entropy over the whole vocabulary by
+        default), or "sampled_ce" (the softmax over the label and K candidates shared by the whole batch,
+        BERTModel.sampled_ce_loss; the batch is (tokens, labels, cand)): single device, steps_per_graph = 1, no
+        vocab_shard.
         overlap (DP, default on unless bucket_numel is given): each gradient bucket's all-reduce starts as soon as the backward has finished it (dp.BucketedExchange);
         bucket_numel: otherwise ONE all-reduce after the backward, in buckets of that many floats.
         vocab_shard (BERT, DP): out.weight / out.bias sharded over the ranks (rbm_amd.vocab_parallel).
@@ -183,15 +187,23 @@ class FusedTrainStep:
         self.kind = model.code()
         if loss is None:
             loss = getattr(model.sas, "sas_loss", "bce") if self.kind == "sas" else None
+            if self.kind == "bert" and getattr(model.bert, "bert_loss", "ce") == "sampled_ce":
+                loss = "sampled_ce"
         if self.kind == "sas":
             if loss not in ("bce", "ce", "sampled_ce"):
                 raise ValueError(f"loss must be 'bce', 'ce' or 'sampled_ce', got {loss!r}")
-        elif loss is not None:
-            raise ValueError(f"loss={loss!r} needs a SAS model (the BERT step has one objective)")
+        elif loss not in (None, "sampled_ce"):
+            raise ValueError(f"loss={loss!r} needs a SAS model (a BERT step takes loss='sampled_ce', or None for the "
+                             "model's own bert_loss: its cross-entropy by default)")
         self.loss = loss
-        if loss in ("ce", "sampled_ce") and (dpx.world() > 1 if dp is None else bool(dp)):
+        dp_on = dpx.world() > 1 if dp is None else bool(dp)
+        if loss in ("ce", "sampled_ce") and dp_on:
             raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
+        if self.kind == "bert" and loss == "sampled_ce" and vocab_shard:
+            raise ValueError("FusedTrainStep(loss='sampled_ce') runs on a single device (vocab_shard is not covered)")
         self.engine = model.sas.engine() if self.kind == "sas" else model.engine()
+        if self.kind == "bert":
+            self.engine.loss = "sampled_ce" if loss == "sampled_ce" else "ce"
         self.flat = self.engine.flat
         self.engine.sync_compute_weights()
         self.engine.external_seed = True       # advanced by the optimizer kernel at the end of each step
@@ -276,7 +288,10 @@ class FusedTrainStep:
         # bounded grid, and joins before the rest of the optimizer (RS_EARLY_HEAD_ADAM=0: at the end, as before).
         self._early_kp = None
         self._early_ev = None
-        self._early_ok = (self.kind == "bert" and not self.dp and self.vshard is None and not self.l2
+        # Not with the sampled-softmax head: it accumulates into a zeroed out.weight / out.bias gradient (no
+        # overwritten range), and its index launches finish on the side stream only at the end of the backward.
+        self._early_ok = (self.kind == "bert" and self.loss != "sampled_ce" and not self.dp and self.vshard is None
+                          and not self.l2
                           and os.environ.get("RS_EARLY_HEAD_ADAM", "1") != "0"
                           and hasattr(self.engine, "overwritten_grads"))
         self._opt_stream = torch.cuda.Stream(device=self.flat.device) if self._early_ok else None
@@ -293,9 +308,12 @@ class FusedTrainStep:
         # with the l2 regulariser (it writes every row); tables below ROW_MARKS_MIN rows are mostly touched.
         # Nor with the full-catalogue CE loss: every table row then has a non-zero gradient.  The sampled softmax's
         # gradient is sparse again, but its head rows come from the fp32 index launch, which stamps nothing: off too.
-        if self.loss in ("ce", "sampled_ce"):
+        # (SAS: its head rows land in the marked table itself.  BERT's sampled head writes out.weight / out.bias, not the
+        # marked token table, whose rows still come from the stamping launch alone: the marks stay on.)
+        tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce")
+        if tied_head:
             self.engine.row_marks = None
-        if (not self.dp and not self.l2 and self.loss not in ("ce", "sampled_ce")
+        if (not self.dp and not self.l2 and not tied_head
                 and os.environ.get("RS_ROW_MARKS", "1") != "0"
                 and hasattr(self.engine, "enable_row_marks")):
             r = self.engine.enable_row_marks(self.ROW_MARKS_MIN)
@@ -420,6 +438,11 @@ class FusedTrainStep:
             dpl, dnl = eng.ws.get("dpl", pl.shape, torch.float32), eng.ws.get("dnl", nl.shape, torch.float32)
             ops.bce_bwd(pl, nl, pos, div, None, dpl, dnl)
             eng.backward(saved, dpl, dnl, self.flat.grad)
+        elif self.loss == "sampled_ce":
+            tokens, labels, cand = batch
+            saved = eng.sce_forward(tokens, labels, cand, True, self.loss_out, max_labelled=self.max_labelled,
+                                    clone_seed=False)
+            eng.sce_backward(saved, self.flat.grad)
         else:
             tokens, labels = batch
             self._maybe_sparse(tokens)
@@ -969,6 +992,10 @@ class FusedTrainStep:
         batch construction included -- as one graph replay (the reference's sampler / DataLoader +
         train_one_epoch body, BS/trainers/base.py:114-123)."""
         want = 3 if self.kind == "sas" else 2
+        if self.kind == "bert" and self.loss == "sampled_ce":
+            if not getattr(sampler, "shared_negs", None):
+                raise ValueError("loss='sampled_ce' needs a sampler with shared_negs=K")
+            want = 3
         if getattr(sampler, "n_outputs", None) != want:
             raise ValueError(f"the {self.kind} step needs a sampler producing {want} tensors")
         S = self._unroll_check(steps_per_graph)
