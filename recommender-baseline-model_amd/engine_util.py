@@ -1,4 +1,6 @@
 """Helpers shared by the SAS and BERT engines."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -68,3 +70,68 @@ def capture_event():
 
 def release_capture_events():
     _CAPTURE_EVENTS.clear()
+
+
+def new_stream(device, avoid=()):
+    """A torch.cuda.Stream whose handle differs from every stream in ``avoid`` and from the current stream.  torch
+    deals its streams round-robin from a pool of 32 per priority, so in a long process a fresh draw can be a stream
+    already in use -- the one being captured, say, which turns every fork onto it into a self-wait and the graph
+    into one chain.  Re-drawn until distinct; RuntimeError after 32 draws."""
+    taken = {s.cuda_stream for s in avoid} | {torch.cuda.current_stream(device).cuda_stream}
+    for _ in range(32):
+        s = torch.cuda.Stream(device=device)
+        if s.cuda_stream not in taken:
+            return s
+    raise RuntimeError(f"no stream of torch's pool is free of the {len(taken)} to avoid")
+
+
+class SideBranch:
+    """One side stream and every fork onto it and join with it: the only place of a training step that touches
+    events.  The engines run the work that needs only the batch's keys or a finished gradient here, beside the main
+    chain (SASEngine.side, BERTEngine.side); FusedTrainStep runs the early optimizer updates on one of its own and
+    warms up and captures on another.  Four rules hold that layout together:
+
+    1. Event lifetime.  Every event is a capture_event(): one made while a stream is capturing outlives the
+       capture (destroyed while the capture still tracks it, it crashed the process).
+    2. Issue order.  A fork is RECORDED early (mark()) but its side work is ISSUED (run(after=mark)) only after the
+       main stream's next launch: a captured graph keeps a node's first child on its queue, so the main chain then
+       stays on the launch queue and the side branch takes the second.  Hence the after_first / after_rows
+       callbacks and the grouped launch before the tail in SASEngine._backward_blocks_fused.  Measured the other way
+       round: SAS cfg2, side branch first, 11 us of fork latency before rs_wgrad_grouped and 11 us of join latency
+       before Adam; BERT cfg3, token index first, ~7 us before the embedding and ~12 us at the token gradient's
+       queue hop (three interleaved rounds: 1.4145 / 1.4142 / 1.4149 -> 1.3983 / 1.4052 / 1.3978 ms/step).
+    3. One writer per table.  All side work on one table goes to the SAME branch, so the table has one writer at a
+       time in a fixed order (sce_backward's head rows, then the lookup rows, joined once).
+    4. Distinct streams.  The side stream is never the stream it forks from: new_stream() draws it apart from the
+       streams given, and run() asserts it against the current one."""
+
+    def __init__(self, device, avoid=()):
+        self.stream = new_stream(device, avoid)
+        self.end = None
+
+    def mark(self):
+        """A fork point: an event recorded on the current stream now."""
+        ev = capture_event()
+        ev.record()
+        return ev
+
+    @contextlib.contextmanager
+    def run(self, after=None, end=True):
+        """Issue the body on the side stream, ordered after the mark ``after`` (None: after the current stream's work
+        so far).  On exit the branch's end event is recorded and kept in ``self.end``; end=False leaves a branch
+        that a later run() continues before anyone joins it."""
+        cur = torch.cuda.current_stream()
+        assert self.stream.cuda_stream != cur.cuda_stream, "a side branch forked from its own stream"
+        if after is not None:
+            self.stream.wait_event(after)
+        else:
+            self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            yield self
+            if end:
+                self.end = capture_event()
+                self.end.record()
+
+    def join(self, ev=None):
+        """The current stream waits for ``ev`` (default: the end of the branch's last run)."""
+        torch.cuda.current_stream().wait_event(ev if ev is not None else self.end)

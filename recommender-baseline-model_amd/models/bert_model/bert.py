@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine_util import Workspace, as_ids, capture_event, compute_dtype, require_cuda, site_salt
+from ...engine_util import SideBranch, Workspace, as_ids, compute_dtype, require_cuda, site_salt
 from ...flat import ALIGN, FlatParams
 
 LN_EPS = 1e-6  # utils/layer_norm.py:8
@@ -185,6 +185,8 @@ class BERTEngine:
         if self.dt == torch.bfloat16:
             flat.enable_bf16()
         self.ws = Workspace(self.dev)
+        # the token index beside the forward, the sampled-softmax head's table rows beside the encoder's backward
+        self.side = SideBranch(self.dev)
         self.seed_base = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.external_seed = False    # True: the fused train step's optimizer advances seed_base
         salt0 = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -391,9 +393,9 @@ class BERTEngine:
         if self._det_table():
             # token-table gradient by inverted index (rs_item_grad: sorted keys, per-row sums, no float
             # atomics -- deterministic); the index comes from the side stream when the step issued it
-            ev, iws = s["side"] if "side" in s else self._token_index(ids, side=False)
+            ev, iws = s["side"] if "side" in s else self._token_index(ids)
             if ev is not None:
-                torch.cuda.current_stream().wait_event(ev)
+                self.side.join(ev)
             ops.embed_bwd(1, ids, T, dx, 1.0, hp, self.salt["emb"], sb, None, G("bert.embedding.position.pe.weight"))
             ops.item_grad(iws, 1, M, dx, 1.0, hp, self.salt["emb"], sb, None, None, None,
                           G("bert.embedding.token.weight"), marks=getattr(self, "row_marks", None))
@@ -468,28 +470,39 @@ class BERTEngine:
                           torch.zeros(1, dtype=torch.uint8, device=self.dev))
         return (name,) + self.row_marks
 
-    def _token_index(self, ids, side=True, after=None):
-        """rs_item_index_build over the batch's token ids (the token-table gradient's inverted index); on a
-        side stream overlapping the forward pass when ``side``, ordered after the event ``after`` (else after the
-        current stream's work).  Returns (event or None, workspace)."""
+    def _token_index(self, ids, after=None):
+        """rs_item_index_build over the batch's token ids (the token-table gradient's inverted index): on the side
+        branch overlapping the forward pass, ordered after the mark ``after``; None: on the current stream.  Returns
+        (the branch's end event or None, workspace)."""
         M = ids.numel()
         rows = self.flat.shapes["bert.embedding.token.weight"][0]
         iws = self.ws.get("tokidx", (ops.item_index_ws_bytes(1, M, rows, self.d),), torch.uint8)
-        if not side:
+        if after is None:
             ops.item_index_build([ids], rows, self.d, iws)
             return None, iws
-        cur = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-        if after is not None:
-            self._side.wait_event(after)
-        else:
-            self._side.wait_stream(cur)
-        with torch.cuda.stream(self._side):
+        with self.side.run(after=after):
             ops.item_index_build([ids], rows, self.d, iws)
-            ev = capture_event()
-            ev.record(self._side)
-        return ev, iws
+        return self.side.end, iws
+
+    def _encode_indexed(self, tokens, training, clone_seed):
+        """encode() with the token index forked onto the side branch: recorded before the first forward launch, issued
+        after it (SideBranch, rule 2).  The saved state's "side" is then (end event, index workspace)."""
+        after_first, side = None, []
+        if self._det_table():
+            fork = self.side.mark()
+
+            def after_first():
+                side.append(self._token_index(tokens, after=fork))
+        xL, s = self.encode(tokens, training, clone_seed=clone_seed, after_first=after_first)
+        if side:
+            s["side"] = side[0]
+        return xL, s
+
+    def _join_index(self, s):
+        """Join the side branch's token index now (before a data-parallel segment ends), not at its use."""
+        if s.get("side") is not None and s["side"][0] is not None:
+            self.side.join(s["side"][0])
+            s["side"] = (None, s["side"][1])
 
     @staticmethod
     def _wgrad_rows(M, shapes, max_tile=256):
@@ -569,24 +582,7 @@ class BERTEngine:
         if ex is not None and split is not None:
             split("tok_ids", lambda: ex.gather_ids(tokens))
             ex.index_rows()
-        # the token index on the side stream, issued after the first forward launch but ordered only after what
-        # preceded it: in a captured graph the forward chain is then the first child of the step's root and keeps
-        # the launch queue, and the side branch takes the second (issued first, it kept the queue and the whole
-        # encoder moved: cfg3 paid ~7 us before the embedding and ~12 us at the token gradient's queue hop;
-        # three interleaved rounds: 1.4145 / 1.4142 / 1.4149 -> 1.3983 / 1.4052 / 1.3978 ms/step)
-        side_box = {}
-        if self._det_table():
-            fork = capture_event()
-            fork.record()
-            side_box["fork"] = fork
-
-        def after_first():
-            if "fork" in side_box:
-                side_box["side"] = self._token_index(tokens, after=side_box["fork"])
-        xL, s = self.encode(tokens, True, clone_seed=False, after_first=after_first)
-        side = side_box.get("side")
-        if side is not None:
-            s["side"] = side
+        xL, s = self._encode_indexed(tokens, True, clone_seed=False)
         B, T = tokens.shape
         M, d = B * T, self.d
         cap = int(max_labelled or M)
@@ -639,10 +635,7 @@ class BERTEngine:
             ops.linear_wgrad(dl, hl, self.flat.view("out.weight", grad), slab, db=self.flat.view("out.bias", grad),
                              rows_dev=cnt, accumulate=False)
         if split is not None:
-            # join the side stream's token index here: a captured graph segment must not end with forked work
-            if s.get("side") is not None and s["side"][0] is not None:
-                torch.cuda.current_stream().wait_event(s["side"][0])
-                s["side"] = (None, s["side"][1])
+            self._join_index(s)         # a captured graph segment must not end with forked work
             split("out")                # the vocabulary head's gradient is final (data-parallel overlap)
         # contraction over the whole vocabulary with few rows: split-K into slabs, then ONE pass that sums
         # the live rows' partials in a fixed order, casts and scatters them back to the token rows
@@ -680,19 +673,7 @@ class BERTEngine:
         cand = cand.reshape(-1).contiguous()
         K = cand.numel()
         _check_shared_negs(K)
-        # the token index on the side stream, after the first forward launch (train_loss_and_backward has the why)
-        side_box = {}
-        if self._det_table():
-            fork = capture_event()
-            fork.record()
-            side_box["fork"] = fork
-
-        def after_first():
-            if "fork" in side_box:
-                side_box["side"] = self._token_index(tokens, after=side_box["fork"])
-        xL, s = self.encode(tokens, training, clone_seed=clone_seed, after_first=after_first)
-        if side_box.get("side") is not None:
-            s["side"] = side_box["side"]
+        xL, s = self._encode_indexed(tokens, training, clone_seed)
         B, T = tokens.shape
         M = B * T
         g = self.ws.get
@@ -715,9 +696,8 @@ class BERTEngine:
         lab_r and dEc[j] at row cand_j of out.weight, coef_r and dbc[j] at those elements of out.bias -- through one
         inverted index over the cap + K keys (rs_item_index_build; rs_item_grad_f32 over {pg, dEc}, then at d = 1 over
         {coef, dbc}: one writer per element, duplicates summed in sorted-entry order, no float atomics).  Those three
-        launches depend on the head alone and run on the side stream beside the encoder's backward, forked after the
-        main stream's next launch is issued (a captured graph keeps a node's first child on its queue) and joined
-        at the end."""
+        launches depend on the head alone and run on the side branch beside the encoder's backward, issued after the
+        main stream's next launch (SideBranch, rule 2) and joined at the end."""
         c = s["sce"]
         d, dt = self.d, self.dt
         f32 = torch.float32
@@ -736,23 +716,16 @@ class BERTEngine:
         # is sized by the entry count alone and the sorted index does not depend on the source width
         rows = max(self.V1, SCE_INDEX_ROWS)
         iws = g("sce_itemidx", (ops.item_index_ws_bytes(1, cap + K, rows, d),), torch.uint8)
-        cur = torch.cuda.current_stream()
-        ev = capture_event()
-        ev.record(cur)
+        fork = self.side.mark()
         dxL = self._buf((M, d))
         ops.splitk_scatter_rows(dh, sk, cap, c["rank"], dxL)
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-        self._side.wait_event(ev)
-        with torch.cuda.stream(self._side):
+        with self.side.run(after=fork):
             ops.item_index_build([keys], rows, d, iws)
             ops.item_grad(iws, 1, cap + K, src, 1.0, 0.0, 0, s["sb"], None, None, None, GW, table_rows=rows)
             ops.item_grad(iws, 1, cap + K, bsrc.view(cap + K, 1), 1.0, 0.0, 0, s["sb"], None, None, None,
                           Gb.view(-1, 1), table_rows=rows)
-            join = capture_event()
-            join.record(self._side)
         self.encode_backward(s, dxL, grad)
-        cur.wait_event(join)
+        self.side.join()
 
     def _sharded_head_and_backward(self, s, xL, hl, lab, idx, rank, cnt, labels, cap, loss_out, grad, split):
         """The vocabulary head with out.weight / out.bias sharded over the data-parallel ranks (vocab_parallel.py):
@@ -776,9 +749,7 @@ class BERTEngine:
             if split is None:
                 action()
             else:
-                if s.get("side") is not None and s["side"][0] is not None:     # join the side stream first
-                    torch.cuda.current_stream().wait_event(s["side"][0])
-                    s["side"] = (None, s["side"][1])
+                self._join_index(s)
                 split(tag, action)
 
         sync("vocab_gather", lambda: (vs.all_gather(H, hl), vs.all_gather(L, lab)))

@@ -40,7 +40,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine_util import Workspace, as_ids, capture_event, compute_dtype, require_cuda, site_salt
+from ...engine_util import SideBranch, Workspace, as_ids, compute_dtype, require_cuda, site_salt
 from ...flat import FlatParams
 
 LN_EPS = 1e-8
@@ -264,6 +264,10 @@ class SASEngine:
         if self.dt == torch.bfloat16:
             flat.enable_bf16()
         self.ws = Workspace(self.dev)
+        # the item index and the transposed weights beside the forward, the item table's gradient beside the grouped
+        # weight gradients, the sampled-softmax head's table rows beside the blocks' backward
+        self.side = SideBranch(self.dev)
+        self._side_refreshed = False
         self.seed_base = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.external_seed = False    # True: the fused train step's optimizer advances seed_base
         # True: the fused train step's optimizer also writes the transposed bf16 block weights (transposed_spec),
@@ -339,8 +343,7 @@ class SASEngine:
         side = fused and training and pos is not None
         nsrc = 1 if ce else 3
         if side:
-            fork = capture_event()
-            fork.record()
+            fork = self.side.mark()
         x = e("x0", (M, d))
         # the fused training step: the head's forward and backward inside the last block's output kernel, the
         # embedding stage inside the first block's input kernel, which counts the valid positions (the BCE divisor)
@@ -358,9 +361,7 @@ class SASEngine:
                           self.salt["emb"], sb, x)
 
         def after_first():
-            if side:
-                # issued after the first forward launch: in the captured graph the forward chain is then the
-                # first child of the step's root and keeps the launch queue; the side branch gets the second
+            if side:     # issued after the first forward launch (SideBranch, rule 2)
                 s["side"] = self._side_prologue(ids, pos, neg, after=fork, nsrc=nsrc)
         head = None
         if cntp is not None:
@@ -484,7 +485,7 @@ class SASEngine:
                 if self._side_refreshed:
                     # the side branch writes the transposed weights during this forward (otherwise the previous
                     # step's optimizer wrote them)
-                    torch.cuda.current_stream().wait_event(s["side"][0])
+                    self.side.join(s["side"][0])
                 tb = self._out_bwd_bufs(s, i)
                 ops.sas_block_out_head_bwd(out_args(i), head, *tb["args"])
                 s["turnaround"] = tb
@@ -555,7 +556,7 @@ class SASEngine:
             if self._side_refreshed:
                 # the blocks' backward reads the transposed weights the side branch wrote this step (otherwise
                 # the previous step's optimizer wrote them)
-                torch.cuda.current_stream().wait_event(ev)
+                self.side.join(ev)
 
             def item_grads(dx):
                 ops.item_grad(iws, 3, M, dx, math.sqrt(d), p, self.salt["emb"], sb, s["f"], dpl, dnl,
@@ -563,7 +564,7 @@ class SASEngine:
             dx = self._backward_blocks_fused(s, dx, grad, segs, tail=item_grads,
                                              pos=lambda dx: (ids, T, dx, p, self.salt["emb"], sb,
                                                              G("pos_emb.weight")) + stats)
-            torch.cuda.current_stream().wait_event(self._tail_join)
+            self.side.join()
             if split is not None:
                 split("dense")          # every parameter gradient is final (data-parallel overlap)
             return len(stats) > 3
@@ -785,13 +786,13 @@ class SASEngine:
             return
         ev, iws = s["side"] if "side" in s else self._side_prologue(ids, None, None, nsrc=1)
         if self._side_refreshed:
-            torch.cuda.current_stream().wait_event(ev)
+            self.side.join(ev)
 
         def item_grads(dx):
             ops.item_grad(iws, 1, M, dx, math.sqrt(d), p, self.salt["emb"], sb, None, None, None, GE)
         self._backward_blocks_fused(s, dx, grad, segs, tail=item_grads,
                                     pos=lambda dx: (ids, T, dx, p, self.salt["emb"], sb, G("pos_emb.weight")))
-        torch.cuda.current_stream().wait_event(self._tail_join)
+        self.side.join()
 
     # ---- sampled softmax over batch-shared candidates (sas_sce.hip) ----------------------------
     def _sce_cand(self, cand):
@@ -851,16 +852,13 @@ class SASEngine:
             ops.item_grad(iws, 1, cap + K, src, 1.0, 0.0, 0, s["sb"], None, None, None, GE, table_rows=rows)
         after_rows = head_table_grad
         if ops.sas_block_fused_ok(d, self.dt) and "side" in s:
-            # the fused path: these launches depend on the head alone, so they run on the side stream beside the
-            # LayerNorm and blocks' backward; the lookup part is issued on the same stream later and the step joins
-            # it (_tail_join), so the table still has one writer at a time, in a fixed order.  Issued after the main
-            # stream's next launch: the captured graph keeps a node's first child on its queue
-            ev = capture_event()
-            ev.record(torch.cuda.current_stream())
+            # the fused path: these launches depend on the head alone, so they run on the side branch beside the
+            # LayerNorm and blocks' backward; the lookup part continues that branch later and the step joins it once
+            # (SideBranch, rules 2 and 3)
+            fork = self.side.mark()
 
             def after_rows():
-                self._side.wait_event(ev)
-                with torch.cuda.stream(self._side):
+                with self.side.run(after=fork, end=False):
                     head_table_grad()
         self._valid_rows_backward(s, grad, dh, sk, after_rows=after_rows)
 
@@ -879,27 +877,18 @@ class SASEngine:
 
     def _side_prologue(self, ids, pos, neg, after=None, nsrc=3):
         """Work of the fused backward that depends only on the batch's keys and the weights, issued on a
-        side stream so it overlaps the forward pass: the item-gradient index (rs_item_index_build) and
-        the transposed block weights (rs_transpose_bf16).  Returns (event, index workspace)."""
-        cur = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-        if after is not None:
-            self._side.wait_event(after)
-        else:
-            self._side.wait_stream(cur)
+        side branch so it overlaps the forward pass: the item-gradient index (rs_item_index_build) and
+        the transposed block weights (rs_transpose_bf16).  Returns (the branch's end event, index workspace)."""
         B, T = ids.shape
         M, d = B * T, self.d
         V1 = self.flat.shapes["item_emb.weight"][0]
-        with torch.cuda.stream(self._side):
+        with self.side.run(after=after):
             iws = self.ws.get("itemidx", (ops.item_index_ws_bytes(nsrc, M, V1, d),), torch.uint8)
             ops.item_index_build([ids, pos, neg][:nsrc], V1, d, iws)
             self._side_refreshed = not self.adam_transposes or self._wT is None
             if self._side_refreshed:
                 self._refresh_transposed()
-            ev = capture_event()
-            ev.record(self._side)
-        return ev, iws
+        return self.side.end, iws
 
     def _refresh_transposed(self):
         """bf16 [in][out] copies of the block weights for the fused backward's input-gradient
@@ -939,9 +928,9 @@ class SASEngine:
         row-local chains; then ALL ten weight gradients and the four LayerNorm affine partial sets in
         one grouped GEMM launch + one grouped reduction (rs_wgrad_grouped, wgrad.hip).  Returns the
         gradient at the embedding output.  tail(dx): work on that gradient alone (the item table's
-        gradient), issued on the side stream so it runs beside the grouped weight-gradient launch (both are
-        latency-bound); the caller joins self._tail_join.  pos(dx): the positional table's gradient (and the head's
-        loss statistics) in the grouped reduction's launch (ops.wgrad_grouped pos=)."""
+        gradient), issued on the side branch so it runs beside the grouped weight-gradient launch (both are
+        latency-bound); the caller joins the branch (self.side.join()).  pos(dx): the positional table's gradient (and
+        the head's loss statistics) in the grouped reduction's launch (ops.wgrad_grouped pos=)."""
         B, T, p, ids, sb = s["B"], s["T"], s["p"], s["ids"], s["sb"]
         M, d, H, Dh, L = B * T, self.d, self.H, self.Dh, self.L
         e = self._buf
@@ -1003,21 +992,12 @@ class SASEngine:
         rows = self._wgrad_rows(M, 6 * L)
         wslab = self.ws.get("wslab", (ops.wgrad_grouped_slab_numel([(d, d)] * 4 * L + [(2 * d, d)] * L, M, rows),),
                             torch.float32)
-        join, fork = None, None
-        if tail is not None:
-            fork = capture_event()
-            fork.record(torch.cuda.current_stream())
-        # the grouped launch is captured BEFORE the side branch: a HIP graph keeps a node's first child on its
-        # queue, so the weight gradients follow the blocks' backward with no cross-queue hop (side branch
-        # first: 11 us of fork latency before rs_wgrad_grouped and 11 us of join latency before Adam)
+        fork = self.side.mark() if tail is not None else None
+        # the grouped launch is issued BEFORE the side branch (SideBranch, rule 2)
         ops.wgrad_grouped(probs, M, rows, wslab, extra=segs, pos=pos(dx) if pos is not None else None)
         if tail is not None:
-            self._side.wait_event(fork)
-            with torch.cuda.stream(self._side):
+            with self.side.run(after=fork):
                 tail(dx)
-                join = capture_event()
-                join.record(self._side)
-            self._tail_join = join
         return dx
 
     @staticmethod

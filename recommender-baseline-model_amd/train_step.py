@@ -28,7 +28,7 @@ import torch
 
 from . import dp as dpx
 from . import ops
-from .engine_util import capture_event, release_capture_events
+from .engine_util import SideBranch, release_capture_events
 
 
 # thread-local capture: the process group's watchdog thread polls its collectives' events while a step graph is
@@ -92,7 +92,7 @@ class FusedAdam:
                               self.hyper, zero_grad=zg, marks=self._marks(lo, hi))
 
 
-    def step_keep_early(self, keep, max_wg=None, zero_grad=False, prep_event=None):
+    def step_keep_early(self, keep, max_wg=None, zero_grad=False):
         """The first part of a step whose `keep` range is final before the rest of the backward (BERT's out.weight /
         out.bias, after the head's dE / dh): rs_adam_prepare (t += 1 and the step's scalars; no seed advance -- the
         backward still draws this step's dropout masks) and that range's update, gradient left in place.
@@ -100,8 +100,6 @@ class FusedAdam:
         lo, hi = keep
         f = self.flat
         ops.adam_prepare(self.state, self.hyper)
-        if prep_event is not None:
-            prep_event.record(torch.cuda.current_stream())
         bf = f.bf16[lo:hi] if f.bf16 is not None else None
         ops.adam_step(f.data[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], bf, self.state, self.hyper,
                       zero_grad=zero_grad, max_wg=max_wg, marks=self._marks(lo, hi))
@@ -284,18 +282,20 @@ class FusedTrainStep:
         self._sparse_checked = False
         # BERT on one device with a vocabulary whose head gradient the backward overwrites whole (overwritten_grads:
         # the 1M-item head): out.weight / out.bias are final once the head's dE / dh are formed, so their Adam update
-        # (256M elements: ~1 ms of HBM streaming at cfg5) runs on a side stream BESIDE the encoder's backward, on a
+        # (256M elements: ~1 ms of HBM streaming at cfg5) runs on a side branch BESIDE the encoder's backward, on a
         # bounded grid, and joins before the rest of the optimizer (RS_EARLY_HEAD_ADAM=0: at the end, as before).
         self._early_kp = None
-        self._early_ev = None
+        self._early_forked = False     # this step forked an early update that _update has yet to join
         # Not with the sampled-softmax head: it accumulates into a zeroed out.weight / out.bias gradient (no
         # overwritten range), and its index launches finish on the side stream only at the end of the backward.
         self._early_ok = (self.kind == "bert" and self.loss != "sampled_ce" and not self.dp and self.vshard is None
                           and not self.l2
                           and os.environ.get("RS_EARLY_HEAD_ADAM", "1") != "0"
                           and hasattr(self.engine, "overwritten_grads"))
-        self._opt_stream = torch.cuda.Stream(device=self.flat.device) if self._early_ok else None
-
+        self._opt_side = SideBranch(dev, avoid=[self.engine.side.stream]) if self._early_ok else None
+        # warmup and graph capture run on a stream that is neither the engine's side stream nor the optimizer's
+        taken = [b.stream for b in (self.engine.side, self._opt_side) if b is not None]
+        self._capture_side = SideBranch(dev, avoid=taken)
         self._early_done = []
         # (below the unzeroed-head vocabulary size -- cfg3's 27k classes -- the early update measured slower: 44.2-44.4k
         # -> 43.6-43.7k seq/s, three interleaved rounds; it runs only with the overwritten-gradient head)
@@ -385,7 +385,7 @@ class FusedTrainStep:
             if not done:
                 # an aborted compute (e.g. a capture failing after the fork) must not leave a forked update for the
                 # next step's _update to join
-                self._early_ev = None
+                self._early_forked = False
                 self._early_done = []
 
     def _compute_impl(self, *batch, split=None):
@@ -505,13 +505,12 @@ class FusedTrainStep:
                     self.rshard.zero_foreign()
                     if post:
                         self._post_update()
-            elif self._early_ev is not None:
+            elif self._early_forked:
                 assert tr is None and kp in (None, self._early_kp), (kp, self._early_kp)
-                cur = torch.cuda.current_stream()
                 done, self._early_done = self._early_done, []
-                cur.wait_event(self._early_ev)
+                self._opt_side.join()
                 self.opt.step_rest(self._early_kp, seed_base=sb, done=done)
-                self._early_ev = None
+                self._early_forked = False
             else:
                 self._l2(self.loss_out[2:3])
                 self.opt.step(seed_base=sb, transposed=tr, keep=kp)
@@ -533,9 +532,10 @@ class FusedTrainStep:
 
     def _early_token_update(self, name):
         """Engine hook (BERTEngine: right after the token table's gradient, before the grouped weight gradients): that
-        range's update follows the early head update on the side stream (same prepared scalars, gradient cleared),
-        beside the grouped weight-gradient launch; step_rest skips it.  Returns True when it forked that update."""
-        if self._early_ev is None:
+        range's update follows the early head update on the optimizer's branch (same prepared scalars, gradient
+        cleared), beside the grouped weight-gradient launch; step_rest skips it.  Returns True when it forked that
+        update."""
+        if not self._early_forked:
             return False
         f = self.flat
         lo = f.offsets[name]
@@ -543,19 +543,14 @@ class FusedTrainStep:
         kp = self._early_kp
         if not (hi <= kp[0] or lo >= kp[1]) or lo % 4:
             return False
-        ev = capture_event()
-        ev.record(torch.cuda.current_stream())
-        self._opt_stream.wait_event(ev)
-        with torch.cuda.stream(self._opt_stream):
+        with self._opt_side.run(after=self._opt_side.mark()):
             self.opt.step_range(lo, hi, zero_grad=True, max_wg=self.EARLY_TOKEN_ADAM_WG)
-            self._early_ev = capture_event()
-            self._early_ev.record(self._opt_stream)
         self._early_done.append((lo, hi))
         return True
 
     def _early_head_update(self):
         """Engine hook (BERTEngine: right after the head's dE / dh): fork the out.weight / out.bias update onto the
-        optimizer's side stream; _update joins it."""
+        optimizer's side branch; _update joins it."""
         rng = self.engine.head_grad_range()
         if rng is None:
             return
@@ -565,14 +560,9 @@ class FusedTrainStep:
             return
         self._early_kp = rng
         self._early_done = []
-        cur = torch.cuda.current_stream()
-        ev = capture_event()
-        ev.record(cur)
-        self._opt_stream.wait_event(ev)
-        with torch.cuda.stream(self._opt_stream):
+        with self._opt_side.run(after=self._opt_side.mark()):
             self.opt.step_keep_early(rng, max_wg=self.EARLY_HEAD_ADAM_WG)
-            self._early_ev = capture_event()
-            self._early_ev.record(self._opt_stream)
+        self._early_forked = True
 
     def _batch(self, batch):
         """loss="ce": neg is ignored and may be None -- pos stands in, so the (seq, pos, neg) buffers keep their form."""
@@ -738,18 +728,20 @@ class FusedTrainStep:
         else:
             self.packed = None
             self.static = [t.clone() for t in example_batch]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.step(*self.static)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        self._warmup(warmup, lambda: self.step(*self.static))
         if S > 1:
             self._capture_graphs(self._unrolled(lambda k: self.static_steps[k]), stamps, unrolled=True)
         else:
             self._capture_graphs(lambda split=None: self._compute(*self.static, split=split, update=True), stamps)
         return self
+
+    def _warmup(self, warmup, step):
+        """`warmup` eager runs of step() on the capture stream; the device is idle afterwards."""
+        with self._capture_side.run():
+            for _ in range(warmup):
+                step()
+        self._capture_side.join()
+        torch.cuda.synchronize()
 
     def _unroll_check(self, steps_per_graph):
         S = int(steps_per_graph)
@@ -857,7 +849,7 @@ class FusedTrainStep:
                 err = None
                 try:
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+                    with torch.cuda.graph(g, stream=self._capture_side.stream, capture_error_mode=CAPTURE_MODE):
                         compute(self._inline_split()) if not unrolled else compute()
                         if not unrolled:
                             self._graph_exchange()
@@ -889,7 +881,7 @@ class FusedTrainStep:
                 self.g_compute = None
             else:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+                with torch.cuda.graph(g, stream=self._capture_side.stream, capture_error_mode=CAPTURE_MODE):
                     compute()
                     if not self.dp and not unrolled:
                         self._update()
@@ -905,7 +897,7 @@ class FusedTrainStep:
             return
         if self.dp:
             self.g_update = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_update, capture_error_mode=CAPTURE_MODE):
+            with torch.cuda.graph(self.g_update, stream=self._capture_side.stream, capture_error_mode=CAPTURE_MODE):
                 self._update(post=False)
         segs = [seg[0] for seg in self.g_segments if seg[0] is not None] if self.g_segments else [self.g_compute]
         self.graphs = tuple(segs) + ((self.g_update,) if self.dp else ())
@@ -913,11 +905,9 @@ class FusedTrainStep:
     def _capture_segments(self, compute):
         """Capture compute(split) as consecutive graphs, a new one begun at every split(tag, action):
         [(graph, tag, action)], the last tagged "final".  At replay, after each graph: its action (a collective of
-        the computation) or its bucket's all-reduce.  All segments share one memory pool and one capture stream."""
+        the computation) or its bucket's all-reduce.  All segments share one memory pool and the capture stream."""
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
         segs, cur = [], [torch.cuda.CUDAGraph()]
         self._empty_graphs = []
 
@@ -937,7 +927,7 @@ class FusedTrainStep:
                 self._empty_graphs.append(cur[0])
                 return None
             return cur[0]
-        with torch.cuda.stream(s):
+        with self._capture_side.run():
             cur[0].capture_begin(pool=pool, capture_error_mode=CAPTURE_MODE)
 
             def split(tag, action=None):
@@ -949,7 +939,7 @@ class FusedTrainStep:
             finally:
                 last = end()
             segs.append((last, "final", None))
-        torch.cuda.current_stream().wait_stream(s)
+        self._capture_side.join()
         torch.cuda.synchronize()
         return segs
 
@@ -1012,15 +1002,7 @@ class FusedTrainStep:
         else:
             self.packed = torch.zeros((want,) + shape, dtype=torch.int64, device=self.flat.device)
             self.static = list(self.packed.unbind(0))
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                sampler.sample_into(*self.static)
-                self.step(*self.static)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-
+        self._warmup(warmup, lambda: (sampler.sample_into(*self.static), self.step(*self.static)))
         if S > 1:
             self._capture_graphs(self._unrolled(lambda k: self.static, lambda: sampler.sample_into(*self.static)),
                                  stamps, unrolled=True)
