@@ -670,14 +670,20 @@ int rs_wgrad_grouped_max(int nprob, const rs_wgrad_problem* probs, int64_t M, in
                          int64_t slab_numel, int nextra, const rs_reduce_segment* extra, int max_tile, void* stream);
 
 /* rs_wgrad_grouped followed by rs_embed_bwd's positional part (bf16, SAS mode 0, scale 1, dpos +=): the
- * positional table's gradient rides in the grouped reduction's launch as T extra workgroups (grad_tail.hip). */
+ * positional table's gradient rides in the grouped reduction's launch as T extra workgroups (grad_tail.hip).
+ * dW, db and the extra segments' outputs are bit-equal to rs_wgrad_grouped's.  dpos is bit-equal to rs_embed_bwd's
+ * for M / T <= 16 sequences; for more the fused launch adds the batch rows in 16 groups where rs_embed_bwd uses 32,
+ * so the two agree within the float32 summation-order bound, not bit for bit (each is deterministic by itself).
+ * Shapes outside the fused form (d > 128 or d % 8, more than 64 segments in all) run the functions one after the
+ * other and give their bits. */
 int rs_wgrad_grouped_pos(int nprob, const rs_wgrad_problem* probs, int64_t M, int64_t rows_per_split, float* slab,
                          int64_t slab_numel, int nextra, const rs_reduce_segment* extra, const int64_t* ids,
                          int64_t T, const void* dx, int64_t d, float drop_p, uint64_t salt,
                          const uint64_t* seed_base, float* dpos, void* stream);
 /* rs_wgrad_grouped_pos whose reduction launch also carries rs_sas_head_finish (one more workgroup): the SAS
  * head's loss statistics loss_out[0..3] from the head's partials (head_part[head_blocks][3]); aux_out (optional,
- * data parallel): (loss sum, count) written there too -- the all-reduced tail of the gradient buffer. */
+ * data parallel): (loss sum, count) written there too -- the all-reduced tail of the gradient buffer.  loss_out
+ * is bit-equal to rs_sas_head_finish's. */
 int rs_wgrad_grouped_pos_stats(int nprob, const rs_wgrad_problem* probs, int64_t M, int64_t rows_per_split,
                                float* slab, int64_t slab_numel, int nextra, const rs_reduce_segment* extra,
                                const int64_t* ids, int64_t T, const void* dx, int64_t d, float drop_p, uint64_t salt,

@@ -1,7 +1,12 @@
 // The SAS backward's gradient tail: rs_wgrad_grouped_pos(_stats) = the grouped weight gradients (wgrad.hip) with
 // the positional table's gradient (embedding.hip, BS/models/sas_model/sas.py:63) and the SAS head's loss statistics
-// (head.hip, BS/trainers/sas.py:49) riding in the grouped reduction's launch -- same arithmetic in the same order,
-// bit for bit, as the functions one after the other (their fallback when the shapes do not fit the fused form).
+// (head.hip, BS/trainers/sas.py:49) riding in the grouped reduction's launch.  Weight and bias gradients, the extra
+// segments' outputs and the loss statistics are the same arithmetic in the same order, bit for bit, as the functions
+// one after the other (their fallback when the shapes do not fit the fused form).  The positional gradient is the
+// same sum in another grouping: embed_pos_body runs here with 16 batch groups (256 threads of the reduction launch),
+// rs_embed_bwd launches it with 32 (512 threads).  Up to 16 sequences every group holds at most one and the bits
+// agree; beyond, the batch rows are added in a different order and dpos agrees with rs_embed_bwd's only within the
+// float32 summation-order bound (tests/test_gradtail_ref_gpu.py holds both to it, and the rest to equal bits).
 // The item table's gradient (itemgrad.hip, rs_item_grad) runs beside it on the step's side queue.
 #include "wgrad.hip"
 #include "itemgrad.hip"
