@@ -847,7 +847,8 @@ int rs_sas_ce_rows_bwd(int dtype, int64_t M, int64_t d, const float* slab, int s
  *   z_rj  = <f_r, E[cand_j]>,  j = 1..K                cand: int64 [K], ids in [0, V]
  *   live(r, j) = cand_j != 0 and cand_j != pos_r       id 0 = an ignored slot; accidental hits masked
  *   loss  = (1 / max(n, 1)) * sum_valid r [ log( exp(z_r0) + sum_{live j} exp(z_rj) ) - z_r0 ],   n = #valid
- * Duplicate ids in cand are separate classes (each counts); no logQ correction; a row with no live candidate has loss
+ * Duplicate ids in cand are separate classes (each counts); no logQ correction in these entries (rs_sce_head_logq_*
+ * below subtract one); a row with no live candidate has loss
  * 0 and gradient 0; an id outside [0, V] counts as 0.  With p_rj = softmax over {0} + live and s = *dloss / *divisor:
  *   dh[r]   = s ((p_r0 - 1) E[pos_r] + sum_live p_rj E[cand_j])     fp32 slabs [splits][cap][d], splits =
  *                                                                   rs_sas_sce_dh_splits(cap, K, d) (host only): one
@@ -907,6 +908,46 @@ int rs_sce_head_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t l
                     const int32_t* count, const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K,
                     const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
                     float* dbc, int64_t* keys, void* stream);
+
+/* ---- the logQ correction of the sampled softmax, and the sampler it describes (sas_sce.hip) ----
+ * rs_sce_head_logq_fwd / _bwd: rs_sce_head_fwd / _bwd with logq, fp32 [V1] or NULL, after bias.  The definition of
+ * rs_sce_head_* with
+ *   z_r0 = <h_r, E[lab_r]>  + b[lab_r]  - logq[lab_r],   z_rj = <h_r, E[cand_j]> + b[cand_j] - logq[cand_j]
+ * (fp32: the dot product plus the one per-id term b[id] - logq[id]; b = 0 without a bias).  live, the loss, lse, dh,
+ * coef, pg, dEc, dbc and keys are computed on these logits exactly as above.  logq is the log of the proposal the
+ * candidates were drawn from; it is not a parameter and gets no gradient.  dbc stays tied to bias alone: required with
+ * a bias, NULL without one, whatever logq is.  logq[0] is never read (id 0 stays the ignored slot; an id outside
+ * [0, V1) counts as 0).  logq == NULL gives rs_sce_head_*'s bits on every output and in ws.  The workspace and slab
+ * counts are rs_sce_head_ws_bytes / rs_sce_head_dh_splits: the correction adds nothing sized by K, cap or V1.
+ *
+ * rs_alias_items: K draws with replacement over [1, item_num] from an alias table (Walker / Vose) of item_num 8-byte
+ * entries, entry s = thr[s] | (uint64_t)alias[s] << 32 with thr[s] a uint32 and alias[s] an item id in [1, item_num].
+ * Draw j, bit for bit (seed = eff_seed(salt, *seed_base) and the constant C = 0x632BE59BD9B4E019 of rs_uniform_items):
+ *   r    = splitmix64(seed + C * (j + 1))                      (64-bit wrap-around arithmetic)
+ *   s    = umulhi(r, item_num)                                 the high 64 bits of r * item_num: the slot, < item_num
+ *   frac = (uint32)((r * item_num mod 2^64) >> 32)             the next 32 bits of the same product
+ *   out[j] = frac < thr[s] ? s + 1 : alias[s]
+ * A slot that keeps its whole mass has alias[s] = s + 1, so thr never has to hold 2^32; with every slot full the draws
+ * are rs_uniform_items' for the same salt and seed.  The distribution the rule realises is fixed by the integers:
+ *   N(v) = thr[v - 1] + sum over {s: alias[s] = v} of (2^32 - thr[s]),    Qhat(v) = N(v) / (item_num * 2^32),
+ * and logq is to be log Qhat (not the log of the weights the table was built from).  How far a uniform 64-bit r lets
+ * the true frequencies sit from Qhat: (s, frac) is floor(r * item_num / 2^32), and the r that land in a run of n
+ * consecutive values of it fill an interval of length n * 2^32 / item_num, which holds within one of that many
+ * integers; item v owns one run in its own slot and one in every slot aliased to it, so
+ *   |P(out[j] = v) - Qhat(v)| < (1 + #{s: alias[s] = v}) * 2^-64,
+ * which is below item_num * 2^-32 per run relative to Qhat(v) even for an item that holds a single cell
+ * (Qhat(v) >= 2^-32 / item_num when N(v) >= 1).
+ * It advances nothing, allocates nothing and is graph-capturable.  K < 1, item_num < 1 or item_num >= 2^32, or a NULL
+ * table / out: RS_ERR_ARG, nothing launched.  The table's aliases are not checked on the device. */
+int rs_sce_head_logq_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                         const int32_t* count, const void* E, const float* bias, const float* logq, int64_t V1,
+                         const int64_t* cand, int64_t K, const float* divisor, void* ws, float* out, void* stream);
+int rs_sce_head_logq_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                         const int32_t* count, const void* E, const float* bias, const float* logq, int64_t V1,
+                         const int64_t* cand, int64_t K, const float* divisor, const float* dloss, void* ws, float* dh,
+                         float* coef, float* pg, float* dEc, float* dbc, int64_t* keys, void* stream);
+int rs_alias_items(const uint64_t* seed_base, uint64_t salt, const uint64_t* table, int64_t item_num, int64_t K,
+                   int64_t* out, void* stream);
 
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);

@@ -207,6 +207,10 @@ SIGNATURES = {
     "rs_sce_head_fwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp],
     "rs_sce_head_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                         vp],
+    "rs_sce_head_logq_fwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp],
+    "rs_sce_head_logq_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                             vp, vp],
+    "rs_alias_items": [vp, u64, vp, i64, i64, vp, vp],
     "rs_kernel_stamps": [vp, vp, i32],
     "rs_kernel_stamp_count": [],
     "rs_kernel_stamp_kinds": [C.POINTER(i32), i32],

@@ -6,8 +6,9 @@
 //   z_rj  = <f_r, E[cand_j]>,  j = 1..K                cand: int64 [K], ids in [0, V]
 //   live(r, j) = cand_j != 0 and cand_j != pos_r       id 0 = an ignored slot; accidental hits masked
 //   loss  = (1 / max(n, 1)) * sum_valid r [ log( exp(z_r0) + sum_{live j} exp(z_rj) ) - z_r0 ],   n = #valid
-// Duplicate candidates are separate classes; there is no logQ correction; a row without a live candidate has loss 0
-// and gradient 0; with cand = 1..V it is the full-catalogue cross-entropy up to the padding class 0 (logit exactly 0),
+// Duplicate candidates are separate classes; the logQ correction is the rs_sce_head_logq_* entries' (below); a row
+// without a live candidate has loss 0 and gradient 0; with cand = 1..V it is the full-catalogue cross-entropy up to
+// the padding class 0 (logit exactly 0),
 // which the full loss counts and a candidate list cannot name.  Gradients, with p = softmax over {0} + live:
 // d f_r = ((p_r0 - 1) E[pos_r] + sum_live p_rj E[cand_j]) / n;  the table gets (p_r0 - 1) / n * f_r at row pos_r and
 // sum_r p_rj / n * f_r at row cand_j.
@@ -38,6 +39,11 @@
 // MFMA sweep (DP = 256: 8 stationary fragments, 16 accumulators per lane, a 33 KB LDS tile); fp32 would need a 67 KB
 // tile and stays on generic_kernel past 128.  Without a bias they give the rs_sas_sce_* entries' bits wherever both run
 // the same kernel.
+//
+// The rs_sce_head_logq_* entries subtract logq[id], the log of the proposal the candidates were drawn from (fp32 [V1],
+// not a parameter): every logit takes the one per-id term b[id] - logq[id] where it took b[id] -- the swept ids' term
+// staged in LDS (forward, dh), the stationary candidate's (dEc), the positive's z0.  The tile loop is the biased
+// head's, and logq == NULL leaves the bits of the entries above.  rs_alias_items draws the candidates from that proposal.
 #include "common.h"
 #include "../../include/recsys_hip.h"
 
@@ -74,7 +80,15 @@ struct Args {
   int64_t rows_per_split;
   const float* bias;   // [V1] or null: added to every logit (rs_sce_head_*)
   float* dbslab;       // dEc role: sum over the split's rows of p per candidate, [splits][K]; null without a bias
+  const float* logq;   // [V1] or null: subtracted from every logit (rs_sce_head_logq_*); not a parameter, no gradient
 };
+
+// the per-id additive term of a logit: bias[id] - logq[id] in fp32 (either may be absent; id != 0, so logq[0] is
+// never read).  With logq null it is bias[id], the bits of the entries without a correction.
+__device__ __forceinline__ float id_term(const Args& a, int32_t id) {
+  const float b = a.bias ? a.bias[id] : 0.f;
+  return a.logq ? b - a.logq[id] : b;
+}
 
 __device__ __forceinline__ int32_t clamp_id(int64_t v, int64_t V1) { return (v <= 0 || v >= V1) ? 0 : (int32_t)v; }
 
@@ -107,10 +121,11 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
   __shared__ float sWlse[TS];
   __shared__ int32_t sSid[TS];
   __shared__ float sScoef[TS];
-  __shared__ float sWb[TS];                           // the swept candidates' bias (forward, dh)
+  __shared__ float sWb[TS];                           // the swept candidates' bias - logq (forward, dh)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
   const int d = a.d;
   const bool vec = a.vec != 0;
+  const bool term = a.bias || a.logq;                 // a per-id term joins the logits
   const int64_t count = a.cnt ? min((int64_t)*a.cnt, a.cap) : a.cap;
   const T* HL = (const T*)a.hl;
   const T* E = (const T*)a.E;
@@ -139,7 +154,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
     }
     z0 += __shfl_xor(z0, 16, 64);
     z0 += __shfl_xor(z0, 32, 64);
-    if (a.bias && sid) z0 += a.bias[sid];
+    if (term && sid) z0 += id_term(a, sid);
   } else if (MODE == DH && sid) {
     slse = a.lse[si];
     z0 = a.z0[si];
@@ -168,8 +183,8 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
   };
   if (w_begin < w_end) tile_ids(w_begin);
   float m = NEG, s = 0.f;
-  // dEc with a bias: the stationary candidate's bias, and this lane's sum of p over the rows it met
-  const float sbias = MODE == DEC && a.bias && sid ? a.bias[sid] : 0.f;
+  // dEc: the stationary candidate's bias - logq, and (with a bias) this lane's sum of p over the rows it met
+  const float sbias = MODE == DEC && term && sid ? id_term(a, sid) : 0.f;
   float psum = 0.f;
   f32x4 O[NT];
 #pragma unroll
@@ -191,7 +206,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
       }
       sWid[tid] = id;
       sWlse[tid] = l;
-      if (MODE != DEC && a.bias) sWb[tid] = id ? a.bias[id] : 0.f;
+      if (MODE != DEC && term) sWb[tid] = id ? id_term(a, id) : 0.f;
     }
     Frag<T> fr[NCH];
 #pragma unroll
@@ -220,7 +235,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(Args a) {
           frag_load_vec(A, &W[(sub * 16 + c) * LDW + kk * 32 + 8 * g]);
           acc = mma(A, S[kk], acc);                   // acc[r] = z[swept sub * 16 + 4 g + r][stationary c]
         }
-        if (a.bias) {
+        if (term) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[r] += MODE == DEC ? sbias : sWb[sub * 16 + 4 * g + r];
         }
@@ -372,7 +387,7 @@ __global__ __launch_bounds__(256) void generic_kernel(Args a) {
       if (k < d) z0 = __builtin_fmaf(sv[i], to_f(prow[k]), z0);
     }
     z0 = wave_sum(z0);
-    if (a.bias) z0 += a.bias[sid];
+    if (a.bias || a.logq) z0 += id_term(a, sid);
   } else if (MODE == DH && sid) {
     slse = a.lse[si];
     z0 = a.z0[si];
@@ -400,7 +415,7 @@ __global__ __launch_bounds__(256) void generic_kernel(Args a) {
       z = __builtin_fmaf(sv[i], wv[i], z);
     }
     z = wave_sum(z);
-    if (a.bias) z += a.bias[cid];
+    if (a.bias || a.logq) z += id_term(a, cid);
     if (MODE == FWD) {
       const float mn = fmaxf(m, z);
       s = s * expf(m - mn) + expf(z - mn);
@@ -556,6 +571,21 @@ __global__ __launch_bounds__(256) void uniform_items_kernel(const uint64_t* seed
   out[j] = 1 + (int64_t)__umul64hi(splitmix64(seed + 0x632BE59BD9B4E019ull * (uint64_t)(j + 1)), (uint64_t)item_num);
 }
 
+// One draw from the packed alias table (entry s = thr[s] | (uint64_t)alias[s] << 32): the high word of r * V picks
+// the slot, the next 32 bits decide between the slot's own item and its alias.
+__global__ __launch_bounds__(256) void alias_items_kernel(const uint64_t* seed_base, uint64_t salt,
+                                                          const uint64_t* __restrict__ table, int64_t item_num,
+                                                          int64_t K, int64_t* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= K) return;
+  const uint64_t seed = eff_seed(salt, seed_base);
+  const uint64_t r = splitmix64(seed + 0x632BE59BD9B4E019ull * (uint64_t)(j + 1));
+  const uint64_t slot = __umul64hi(r, (uint64_t)item_num);          // < item_num
+  const uint32_t frac = (uint32_t)((r * (uint64_t)item_num) >> 32);
+  const uint64_t e = table[slot];
+  out[j] = frac < (uint32_t)e ? (int64_t)slot + 1 : (int64_t)(e >> 32);
+}
+
 static int splits_of(int64_t cap, int64_t K, int64_t* rows_per_split) {
   const int64_t nct = cdiv(K, (int64_t)TS), tiles = cdiv(cap, (int64_t)TS);
   int64_t sp = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(MAX_SPLITS, tiles), cdiv(512, nct)));
@@ -629,8 +659,8 @@ static void launch(int dtype, int64_t d, int64_t items, int ysplits, hipStream_t
 }
 
 static int fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab, const int32_t* count,
-               const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K, const float* divisor,
-               void* ws, float* out, void* stream, bool wide) {
+               const void* E, const float* bias, const float* logq, int64_t V1, const int64_t* cand, int64_t K,
+               const float* divisor, void* ws, float* out, void* stream, bool wide) {
   if (!supported(dtype, d, K)) return RS_ERR_UNSUPPORTED;
   if (cap <= 0 || cap >= ((int64_t)1 << 31) || V1 < 1 || V1 >= ((int64_t)1 << 31) || !hl || !lab || !E || !cand ||
       !divisor || !ws || !out || ldh < d || !al16(ws))
@@ -640,6 +670,7 @@ static int fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, c
   a.hl = hl; a.ldh = ldh; a.lab = lab; a.cnt = count; a.cap = cap; a.E = E; a.V1 = V1; a.cand = cand; a.K = K;
   a.d = (int)d;
   a.bias = bias;
+  a.logq = logq;
   a.vec = al16(hl) && al16(E) && (ldh * sz) % 16 == 0 && (d * sz) % 16 == 0;
   const WsLayout L = ws_layout(cap, K, d);
   a.lse = (float*)ws;
@@ -656,9 +687,9 @@ static int fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, c
 }
 
 static int bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab, const int32_t* count,
-               const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K, const float* divisor,
-               const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc, float* dbc, int64_t* keys,
-               void* stream, bool wide) {
+               const void* E, const float* bias, const float* logq, int64_t V1, const int64_t* cand, int64_t K,
+               const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
+               float* dbc, int64_t* keys, void* stream, bool wide) {
   if (!supported(dtype, d, K)) return RS_ERR_UNSUPPORTED;
   if (cap <= 0 || cap >= ((int64_t)1 << 31) || V1 < 1 || V1 >= ((int64_t)1 << 31) || !hl || !lab || !E || !cand ||
       !divisor || !ws || !dh || !coef || !pg || !dEc || ldh < d || !al16(ws))
@@ -668,6 +699,7 @@ static int bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, c
   a.hl = hl; a.ldh = ldh; a.lab = lab; a.cnt = count; a.cap = cap; a.E = E; a.V1 = V1; a.cand = cand; a.K = K;
   a.d = (int)d;
   a.bias = bias;
+  a.logq = logq;
   a.vec = al16(hl) && al16(E) && (ldh * sz) % 16 == 0 && (d * sz) % 16 == 0;
   a.lse = (float*)ws;
   a.z0 = a.lse + cap;
@@ -715,15 +747,16 @@ int64_t rs_sas_sce_dh_splits(int64_t cap, int64_t K, int64_t d) {
 int rs_sas_sce_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
                    const int32_t* count, const void* E, int64_t V1, const int64_t* cand, int64_t K,
                    const float* divisor, void* ws, float* out, void* stream) {
-  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, nullptr, V1, cand, K, divisor, ws, out, stream, false);
+  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, nullptr, nullptr, V1, cand, K, divisor, ws, out, stream,
+                  false);
 }
 
 int rs_sas_sce_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
                    const int32_t* count, const void* E, int64_t V1, const int64_t* cand, int64_t K,
                    const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
                    int64_t* keys, void* stream) {
-  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, nullptr, V1, cand, K, divisor, dloss, ws, dh, coef, pg, dEc,
-                  nullptr, keys, stream, false);
+  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, nullptr, nullptr, V1, cand, K, divisor, dloss, ws, dh, coef,
+                  pg, dEc, nullptr, keys, stream, false);
 }
 
 int64_t rs_sce_head_ws_bytes(int dtype, int64_t cap, int64_t K, int64_t d, int has_bias) {
@@ -744,7 +777,7 @@ int rs_sce_head_path(int dtype, int64_t d) {
 int rs_sce_head_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
                     const int32_t* count, const void* E, const float* bias, int64_t V1, const int64_t* cand, int64_t K,
                     const float* divisor, void* ws, float* out, void* stream) {
-  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, bias, V1, cand, K, divisor, ws, out, stream, true);
+  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, bias, nullptr, V1, cand, K, divisor, ws, out, stream, true);
 }
 
 int rs_sce_head_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
@@ -752,8 +785,31 @@ int rs_sce_head_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t l
                     const float* divisor, const float* dloss, void* ws, float* dh, float* coef, float* pg, float* dEc,
                     float* dbc, int64_t* keys, void* stream) {
   if (!bias != !dbc) return sce::supported(dtype, d, K) ? RS_ERR_ARG : RS_ERR_UNSUPPORTED;
-  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, bias, V1, cand, K, divisor, dloss, ws, dh, coef, pg, dEc, dbc,
-                  keys, stream, true);
+  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, bias, nullptr, V1, cand, K, divisor, dloss, ws, dh, coef, pg,
+                  dEc, dbc, keys, stream, true);
+}
+
+int rs_sce_head_logq_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                         const int32_t* count, const void* E, const float* bias, const float* logq, int64_t V1,
+                         const int64_t* cand, int64_t K, const float* divisor, void* ws, float* out, void* stream) {
+  return sce::fwd(dtype, cap, d, hl, ldh, lab, count, E, bias, logq, V1, cand, K, divisor, ws, out, stream, true);
+}
+
+int rs_sce_head_logq_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                         const int32_t* count, const void* E, const float* bias, const float* logq, int64_t V1,
+                         const int64_t* cand, int64_t K, const float* divisor, const float* dloss, void* ws, float* dh,
+                         float* coef, float* pg, float* dEc, float* dbc, int64_t* keys, void* stream) {
+  if (!bias != !dbc) return sce::supported(dtype, d, K) ? RS_ERR_ARG : RS_ERR_UNSUPPORTED;
+  return sce::bwd(dtype, cap, d, hl, ldh, lab, count, E, bias, logq, V1, cand, K, divisor, dloss, ws, dh, coef, pg,
+                  dEc, dbc, keys, stream, true);
+}
+
+int rs_alias_items(const uint64_t* seed_base, uint64_t salt, const uint64_t* table, int64_t item_num, int64_t K,
+                   int64_t* out, void* stream) {
+  if (item_num < 1 || item_num >= ((int64_t)1 << 32) || K < 1 || !table || !out) return RS_ERR_ARG;
+  hipLaunchKernelGGL(sce::alias_items_kernel, dim3((unsigned)cdiv(K, (int64_t)256)), dim3(256), 0,
+                     (hipStream_t)stream, seed_base, salt, table, item_num, K, out);
+  return (int)hipGetLastError();
 }
 
 int rs_uniform_items(const uint64_t* seed_base, uint64_t salt, int64_t item_num, int64_t K, int64_t* out, void* stream) {

@@ -16,7 +16,15 @@ the users in a fresh random order (``torch.randperm`` on the device at ``__iter_
 n_users // batch_size`` full batches (the fixed batch shape a captured graph needs; the reference's
 last partial batch is dropped), each row = that user's last ``max_len`` items cloze-masked at
 ``mask_prob`` (80 % [MASK] = num_items+1, 10 % random item, 10 % kept), labels = the masked items.
+
+ItemProposal: a non-uniform proposal over the items for the shared candidates of the sampled softmax (popularity
+sampling, the reference's ``negative_samplers/popular.py`` moved into the loss): a fixed-point alias table the
+device draws from (rs_alias_items) and the log of the distribution those draws realise, which the loss subtracts
+from every logit (the logQ correction; ``sampled_ce_loss(..., logq=)``).
 """
+import math
+
+import numpy as np
 import torch
 
 from . import ops
@@ -32,21 +40,123 @@ def _flatten(histories, device):
     return off.to(device), items, len(lens)
 
 
+class ItemProposal:
+    """Q(v) = w_v / sum(w) over the items 1..V, as a Walker / Vose alias table in fixed point.
+
+    Slot s in [0, V) holds thr[s] (uint32) and alias[s] (an item id in [1, V]); a draw picks a slot uniformly and
+    returns s + 1 with probability thr[s] / 2^32, else alias[s] (rs_alias_items gives the rule bit for bit).  A slot
+    that keeps its whole mass has alias[s] = s + 1 (and thr[s] = 0), so thr never has to hold 2^32.
+
+    The build, in float64 and deterministic (same weights, same table): p_s = w_(s+1) * V / fsum(w); the slots with
+    p < 1 and those with p >= 1 go on two stacks in ascending order; while both hold one, the top small s and the
+    top large l are popped, slot s keeps p_s and is aliased to l + 1, p_l becomes (p_l + p_s) - 1 and l goes back on
+    the stack its new p belongs to; what is left keeps its whole mass.  thr[s] = max(1, floor(p_s * 2^32)) for an
+    aliased slot, so every item keeps at least one of the V * 2^32 cells.
+
+    The draw rule then fixes the distribution that is actually sampled, in integers:
+        N(v) = thr[v - 1] + sum over {s: alias[s] = v} of (2^32 - thr[s]),    Qhat(v) = N(v) / (V * 2^32)
+    .q is Qhat (float64, host, [V + 1], entry 0 = 0), .logq is log Qhat computed in float64 from the integers (fp32,
+    on the device, entry 0 = 0) -- not the log of the float weights: the correction describes the sampler that runs.
+    .table is the packed device table, int64 [V]: thr[s] | alias[s] << 32."""
+
+    def __init__(self, weights, device="cuda"):
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim != 1 or w.shape[0] < 2:
+            raise ValueError("weights must be a 1-D array of item_num + 1 entries (entry 0 is ignored)")
+        V = w.shape[0] - 1
+        if V >= 2 ** 31:
+            raise ValueError("item_num must be below 2^31")
+        w = w[1:]
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError("the weights of the items 1..V must be finite and strictly positive (an item with Q = 0 "
+                             "could still be a positive, and its corrected logit would be +inf)")
+        total = math.fsum(w.tolist())
+        if not math.isfinite(total):
+            raise ValueError("the weights overflow float64 when summed")
+        self.item_num = V
+        self.weights = np.concatenate([[0.0], w])
+        thr, alias = _alias_table(w, total)
+        self.thr, self.alias = thr, alias
+        n = thr.astype(np.uint64)
+        np.add.at(n, alias - 1, np.uint64(1 << 32) - thr.astype(np.uint64))
+        self.counts = n                                             # N(v), v = 1..V; sums to V * 2^32
+        cells = np.uint64(V << 32)
+        qv = n.astype(np.float64) / float(V << 32)
+        rest = (cells - n).astype(np.float64) / float(V << 32)       # 1 - Qhat from the integers: no cancellation
+        logq = np.where(qv > 0.5, np.log1p(-rest), np.log(qv))        # accurate to float64 near Qhat = 1 as well
+        self.q = np.concatenate([[0.0], qv])
+        self.device = torch.device(device)
+        self.logq = torch.from_numpy(np.concatenate([[0.0], logq]).astype(np.float32)).to(self.device)
+        packed = thr.astype(np.uint64) | (alias.astype(np.uint64) << np.uint64(32))
+        self.table = torch.from_numpy(packed.view(np.int64).copy()).to(self.device)
+
+    @classmethod
+    def from_histories(cls, histories, item_num, alpha=1.0, smooth=1.0, device="cuda"):
+        """w_v = (count_v + smooth) ** alpha, count_v = the occurrences of item v in histories (the user_train /
+        u2seq the samplers take).  alpha = 0 is the uniform proposal."""
+        item_num = int(item_num)
+        flat = np.fromiter((i for s in histories for i in s), dtype=np.int64)
+        if flat.size and (flat.min() < 1 or flat.max() > item_num):
+            raise ValueError("histories hold an item id outside [1, item_num]")
+        count = np.bincount(flat, minlength=item_num + 1).astype(np.float64)
+        w = (count + float(smooth)) ** float(alpha)
+        w[0] = 0.0
+        return cls(w, device=device)
+
+
+def _alias_table(w, total):
+    """(thr uint32 [V], alias int64 [V]) of ItemProposal's build over the weights w [V] (float64) with sum total."""
+    V = w.shape[0]
+    p = (w * float(V) / total).tolist()
+    small = [s for s in range(V) if p[s] < 1.0]
+    large = [s for s in range(V) if not p[s] < 1.0]
+    keep = [1.0] * V
+    alias = list(range(1, V + 1))
+    while small and large:
+        s, l = small.pop(), large.pop()
+        keep[s] = p[s]
+        alias[s] = l + 1
+        pl = (p[l] + p[s]) - 1.0
+        p[l] = pl
+        (small if pl < 1.0 else large).append(l)
+    alias = np.asarray(alias, dtype=np.int64)
+    own = alias == np.arange(1, V + 1)
+    thr = np.maximum(np.floor(np.asarray(keep) * 2.0 ** 32), 1.0)
+    thr = np.where(own, 0.0, thr).astype(np.uint32)
+    return thr, alias
+
+
+def _check_proposal(proposal, shared_negs, item_num, device):
+    if proposal is None:
+        return
+    if shared_negs is None:
+        raise ValueError("proposal needs shared_negs=K: it draws the shared candidates")
+    if proposal.item_num != item_num:
+        raise ValueError(f"proposal.item_num = {proposal.item_num}, the sampler's item number is {item_num}")
+    pd = proposal.table.device
+    if pd.type != device.type or (device.index is not None and pd.index != device.index):
+        raise ValueError(f"the proposal lives on {proposal.table.device}, the sampler on {device}")
+
+
 class DeviceWarpSampler:
     n_outputs = 3
 
     def __init__(self, user_train, item_num, batch_size, max_len, device="cuda", num_workers=None, seed=None,
-                 shared_negs=None):
+                 shared_negs=None, proposal=None):
         """user_train: list (per user) of item-id lists, as ``data_partition`` builds it.
         num_workers is accepted for signature compatibility and ignored.
         shared_negs=K: batches are (seq, pos, cand) with cand int64 (K,) drawn uniformly with replacement from
         [1, item_num] on the device (rs_uniform_items: the same advanced step seed, its own salt) -- the candidates
-        of the sampled-softmax loss, shared by the whole batch; the per-position neg goes to a private buffer."""
+        of the sampled-softmax loss, shared by the whole batch; the per-position neg goes to a private buffer.
+        proposal (an ItemProposal over item_num items, with shared_negs): cand is drawn from it instead
+        (rs_alias_items, same seed, same salt); .proposal.logq is the correction the loss then needs."""
         if max_len > 512:
             raise ValueError("max_len must be <= 512")
         self.device = torch.device(device)
         self.offsets, self.items, self.n_users = _flatten(user_train, self.device)
         self.item_num = int(item_num)
+        _check_proposal(proposal, shared_negs, self.item_num, self.device)
+        self.proposal = proposal
         self.batch_size = int(batch_size)
         self.max_len = int(max_len)
         self.num_batch = self.n_users // self.batch_size
@@ -70,7 +180,10 @@ class DeviceWarpSampler:
                 raise ValueError(f"cand must be a contiguous int64 tensor of shape ({self.shared_negs},)")
             ops.sas_sample(self.offsets, self.items, self.n_users, self.item_num, self.seed_base, self.salt, seq, pos,
                            self._neg, draws)
-            ops.uniform_items(self.seed_base, self.cand_salt, self.item_num, cand)   # the seed the launch above advanced
+            if self.proposal is not None:                       # the seed the launch above advanced, either way
+                ops.alias_items(self.seed_base, self.cand_salt, self.proposal.table, cand)
+            else:
+                ops.uniform_items(self.seed_base, self.cand_salt, self.item_num, cand)
             return
         ops.sas_sample(self.offsets, self.items, self.n_users, self.item_num, self.seed_base, self.salt, seq, pos, neg,
                        draws)
@@ -107,12 +220,15 @@ class DeviceWarpSampler:
 class DeviceBertMasker:
     n_outputs = 2
 
-    def __init__(self, u2seq, num_items, batch_size, max_len, mask_prob, device="cuda", seed=None, shared_negs=None):
+    def __init__(self, u2seq, num_items, batch_size, max_len, mask_prob, device="cuda", seed=None, shared_negs=None,
+                 proposal=None):
         """u2seq: list (per user) of training item-id lists (the reference's ``train`` dict values in user
         order).  The [MASK] token is num_items + 1, as BERTEmbedding's table (V+2 rows) expects.
         shared_negs=K: batches are (tokens, labels, cand) with cand int64 (K,) drawn uniformly with replacement from
         [1, num_items] on the device (rs_uniform_items on the step seed rs_bert_mask advanced, its own salt) -- the
-        candidates of the sampled-softmax loss, shared by the whole batch."""
+        candidates of the sampled-softmax loss, shared by the whole batch.
+        proposal (an ItemProposal over num_items items, with shared_negs): cand is drawn from it instead
+        (rs_alias_items, same seed, same salt); .proposal.logq is the correction the loss then needs."""
         self.shared_negs = None if shared_negs is None else int(shared_negs)
         if self.shared_negs is not None and self.shared_negs < 1:
             raise ValueError("shared_negs must be a positive number of candidates")
@@ -120,6 +236,8 @@ class DeviceBertMasker:
         self.device = torch.device(device)
         self.offsets, self.items, self.n_users = _flatten(u2seq, self.device)
         self.num_items = int(num_items)
+        _check_proposal(proposal, shared_negs, self.num_items, self.device)
+        self.proposal = proposal
         self.batch_size = int(batch_size)
         self.max_len = int(max_len)
         self.mask_prob = float(mask_prob)
@@ -156,8 +274,10 @@ class DeviceBertMasker:
         draws = rest[0] if rest else draws
         ops.bert_mask(self.offsets, self.items, self.n_users, self.num_items, self.mask_prob, self.perm, self.state,
                       self.salt, tokens, labels, draws)
-        if cand is not None:
-            ops.uniform_items(self.state[0:1], self.cand_salt, self.num_items, cand)   # the seed just advanced
+        if cand is not None and self.proposal is not None:      # the seed just advanced, either way
+            ops.alias_items(self.state[0:1], self.cand_salt, self.proposal.table, cand)
+        elif cand is not None:
+            ops.uniform_items(self.state[0:1], self.cand_salt, self.num_items, cand)
 
     def sample(self):
         shape = (self.batch_size, self.max_len)

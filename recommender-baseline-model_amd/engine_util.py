@@ -32,6 +32,35 @@ def require_cuda(device):
             "set args.device='cuda' (there is no CPU fallback)")
 
 
+NEG_DISTS = ("uniform", "popular")
+
+
+def neg_dist_args(args, prefix, loss):
+    """(dist, alpha) from ``args.<prefix>_neg_dist`` ('uniform', the default, or 'popular') and
+    ``args.<prefix>_neg_alpha`` (default 1.0): the proposal the sampled softmax's shared candidates come from.
+    'popular' describes those candidates alone, so it needs ``<prefix>_loss = 'sampled_ce'``."""
+    dist = str(getattr(args, prefix + "_neg_dist", None) or "uniform")
+    if dist not in NEG_DISTS:
+        raise ValueError(f"{prefix}_neg_dist must be one of {NEG_DISTS}, got {dist!r}")
+    if dist == "popular" and loss != "sampled_ce":
+        raise ValueError(f"{prefix}_neg_dist='popular' needs {prefix}_loss='sampled_ce' (it draws the shared candidates)")
+    alpha = getattr(args, prefix + "_neg_alpha", None)
+    alpha = 1.0 if alpha is None else float(alpha)
+    if not np.isfinite(alpha):
+        raise ValueError(f"{prefix}_neg_alpha must be finite, got {alpha!r}")
+    return dist, alpha
+
+
+def check_logq(logq, E):
+    """The logQ correction of a sampled-softmax call: None, or fp32 [rows of E], contiguous, on E's device."""
+    if logq is None:
+        return None
+    if not isinstance(logq, torch.Tensor) or logq.dtype != torch.float32 or tuple(logq.shape) != (E.shape[0],) \
+            or not logq.is_contiguous() or logq.device != E.device:
+        raise ValueError(f"logq must be a contiguous fp32 tensor of shape ({E.shape[0]},) on {E.device}")
+    return logq
+
+
 def site_salt(base, site):
     """Distinct 64-bit dropout salt per (model instance, dropout site)."""
     return (int(base) * 0x100000001B3 + 0x9E3779B97F4A7C15 * (site + 1)) & 0xFFFFFFFFFFFFFFFF

@@ -70,7 +70,7 @@ class BERTModel(BaseModel):
         dev = self._flat.device
         return self.engine().full_rank(as_ids(x, dev), as_ids(target, dev).reshape(-1), exclude_seen)
 
-    def sampled_ce_loss(self, tokens, labels, cand):
+    def sampled_ce_loss(self, tokens, labels, cand, logq=None):
         """Scalar loss of the sampled softmax over batch-shared candidates (differentiable; available whatever
         bert_loss says).  cand: int64 (K,), shared by every position; with E = out.weight, b = out.bias:
 
@@ -80,8 +80,11 @@ class BERTModel(BaseModel):
             live(r, j) = cand_j != 0 and cand_j != labels_r    id 0 = an ignored slot; accidental hits masked
             loss  = (1 / max(n, 1)) * sum_r [ log(exp(z_r0) + sum_{live j} exp(z_rj)) - z_r0 ],   n = #labelled
 
-        Duplicate candidates count separately; an id outside out.weight's rows counts as 0; there is no logQ
-        correction (a log-probability added to the bias is the hook for one).  With cand = every item it is the
+        Duplicate candidates count separately; an id outside out.weight's rows counts as 0.  logq (fp32, one entry
+        per row of out.weight, on the device: ItemProposal.logq) is the logQ correction, the log of the distribution
+        the candidates were drawn from: z_r0 -= logq[labels_r], z_rj -= logq[cand_j]; a constant of the loss (no
+        gradient, and out.bias's gradient is unchanged in form), entry 0 never read; None: no correction.  With
+        cand = every item it is the
         reference's cross-entropy up to class 0, which that loss counts and no candidate list can name.  A row with
         no live candidate, and a batch with no labelled row, give loss 0 and zero gradients; rows of out.weight /
         out.bias outside the batch's labels and candidates get none.  Call backward() before the next loss call."""
@@ -89,7 +92,7 @@ class BERTModel(BaseModel):
         dev = self._flat.device
         ids, lab, cand = as_ids(tokens, dev), as_ids(labels, dev), as_ids(cand, dev)
         params = [p for _, p in self.named_parameters()]
-        return _BERTSCEFunction.apply(eng, ids, lab, cand, self.training, *params)
+        return _BERTSCEFunction.apply(eng, ids, lab, cand, logq, self.training, *params)
 
     def forward(self, x):
         eng = self.engine()

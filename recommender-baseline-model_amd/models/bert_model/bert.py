@@ -36,7 +36,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine_util import SideBranch, Workspace, as_ids, compute_dtype, require_cuda, site_salt
+from ...engine_util import (SideBranch, Workspace, as_ids, check_logq, compute_dtype, neg_dist_args, require_cuda,
+                            site_salt)
 from ...flat import ALIGN, FlatParams
 
 LN_EPS = 1e-6  # utils/layer_norm.py:8
@@ -133,6 +134,9 @@ class BERT(nn.Module):
             if getattr(args, "bert_shared_negs", None) is None:
                 raise ValueError("bert_loss='sampled_ce' needs args.bert_shared_negs = K (the shared candidates)")
             _check_shared_negs(self.bert_shared_negs)
+        # the proposal the shared candidates are drawn from: "uniform", or "popular" (an ItemProposal over the
+        # training counts ** bert_neg_alpha, handed to the masker; the loss then takes its logq correction)
+        self.bert_neg_dist, self.bert_neg_alpha = neg_dist_args(args, "bert", self.bert_loss)
         vocab_size = args.num_items + 2          # [MASK] = num_items + 1, padding = 0
         self.embedding = BERTEmbedding(vocab_size=vocab_size, embed_size=self.hidden, max_len=self.max_len)
         self.transformer_blocks = nn.ModuleList(
@@ -658,12 +662,14 @@ class BERTEngine:
 
 
     # ---- sampled softmax over batch-shared candidates (sas_sce.hip, rs_sce_head_*) -----------------
-    def sce_forward(self, tokens, labels, cand, training, loss_out, max_labelled=None, clone_seed=True):
+    def sce_forward(self, tokens, labels, cand, training, loss_out, max_labelled=None, clone_seed=True, logq=None):
         """Encoder forward, then on the labelled rows only the softmax cross-entropy of the label against the K
         candidates `cand` (int64 [K], shared by every row; id 0 and a row's own label are masked;
         BERTModel.sampled_ce_loss has the definition) with E = out.weight, bias = out.bias.  loss_out = {loss sum,
         labelled count, mean}; the divisor is max(count, 1).  Returns the saved state for sce_backward.  The sce_*
-        buffers are sized by (cap, K, d) alone; nothing here allocates per step or reads the host."""
+        buffers are sized by (cap, K, d) alone; nothing here allocates per step or reads the host.  logq (fp32
+        [out.weight's rows], device): the proposal's correction, subtracted from every logit beside the bias
+        (rs_sce_head_logq_*); sce_backward reads it from the saved state."""
         d, dt = self.d, self.dt
         if dt == torch.bfloat16 and d % 8:
             raise ValueError(f"the bf16 sampled-softmax head needs hidden units divisible by 8 (got {d}); "
@@ -673,6 +679,7 @@ class BERTEngine:
         cand = cand.reshape(-1).contiguous()
         K = cand.numel()
         _check_shared_negs(K)
+        logq = check_logq(logq, self.W("out.weight"))
         xL, s = self._encode_indexed(tokens, training, clone_seed)
         B, T = tokens.shape
         M = B * T
@@ -686,8 +693,9 @@ class BERTEngine:
         div.copy_(cnt)
         div.clamp_(min=1.0)                       # an all-unlabelled batch: loss 0, zero gradients
         ws = g("sce_ws", (ops.sce_head_ws_numel(cap, K, d, dt),), torch.float32)
-        ops.sce_head_fwd(hl, lab, cnt, cap, self.W("out.weight"), self.Wf("out.bias"), cand, div, ws, loss_out)
-        s.update(sce=dict(cap=cap, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, ws=ws, cand=cand))
+        ops.sce_head_fwd(hl, lab, cnt, cap, self.W("out.weight"), self.Wf("out.bias"), cand, div, ws, loss_out,
+                         logq=logq)
+        s.update(sce=dict(cap=cap, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, ws=ws, cand=cand, logq=logq))
         return s
 
     def sce_backward(self, s, grad, dloss=None):
@@ -711,7 +719,7 @@ class BERTEngine:
         src, bsrc = g("sce_src", (cap + K, d), f32), g("sce_bsrc", (cap + K,), f32)
         keys = g("sce_keys", (cap + K,), torch.int64)
         ops.sce_head_bwd(hl, lab, cnt, cap, self.W("out.weight"), self.Wf("out.bias"), cand, c["div"], dloss, c["ws"],
-                         dh, bsrc[:cap], src[:cap], src[cap:], bsrc[cap:], keys)
+                         dh, bsrc[:cap], src[:cap], src[cap:], bsrc[cap:], keys, logq=c["logq"])
         # the index's key range: past the counting sort's table limit, so that the radix path is taken, the workspace
         # is sized by the entry count alone and the sorted index does not depend on the source width
         rows = max(self.V1, SCE_INDEX_ROWS)
@@ -805,10 +813,10 @@ class _BERTFunction(torch.autograd.Function):
 
 class _BERTSCEFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, engine, ids, labels, cand, training, *params):
+    def forward(ctx, engine, ids, labels, cand, logq, training, *params):
         engine.sync_compute_weights()
         out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
-        ctx.saved = engine.sce_forward(ids, labels, cand, training, out)
+        ctx.saved = engine.sce_forward(ids, labels, cand, training, out, logq=logq)
         ctx.engine = engine
         return out[2].clone()
 
@@ -818,7 +826,8 @@ class _BERTSCEFunction(torch.autograd.Function):
         grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
         eng.sce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
         ctx.saved = None
-        return (None, None, None, None, None, *[eng.flat.view(n, grad) for n in eng.flat.names_in_module_order])
+        return (None, None, None, None, None, None,
+                *[eng.flat.view(n, grad) for n in eng.flat.names_in_module_order])
 
 
 def build_flat(model, device):

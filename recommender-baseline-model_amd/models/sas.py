@@ -18,8 +18,8 @@ class SASModel(BaseModel):
     def ce_loss(self, log_seqs, pos_seqs):  # full-catalogue softmax cross-entropy, item table tied (SAS.ce_loss)
         return self.sas.ce_loss(log_seqs, pos_seqs)
 
-    def sampled_ce_loss(self, log_seqs, pos_seqs, cand):  # softmax over the positive + K batch-shared candidates
-        return self.sas.sampled_ce_loss(log_seqs, pos_seqs, cand)
+    def sampled_ce_loss(self, log_seqs, pos_seqs, cand, logq=None):  # softmax over the positive + K shared candidates
+        return self.sas.sampled_ce_loss(log_seqs, pos_seqs, cand, logq=logq)  # logq: the proposal's correction
 
     def predict(self, log_seqs, item_indices):  # for inference
         return self.sas.predict(log_seqs, item_indices)

@@ -40,7 +40,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine_util import SideBranch, Workspace, as_ids, compute_dtype, require_cuda, site_salt
+from ...engine_util import (SideBranch, Workspace, as_ids, check_logq, compute_dtype, neg_dist_args, require_cuda,
+                            site_salt)
 from ...flat import FlatParams
 
 LN_EPS = 1e-8
@@ -80,6 +81,9 @@ class SAS(nn.Module):
         self.sas_shared_negs = int(getattr(args, "sas_shared_negs", 0) or 0)
         if self.sas_loss == "sampled_ce" and self.sas_shared_negs < 1:
             raise ValueError("sas_loss='sampled_ce' needs args.sas_shared_negs = K > 0 (the shared candidates)")
+        # the proposal the shared candidates are drawn from: "uniform", or "popular" (an ItemProposal over the
+        # training counts ** sas_neg_alpha, handed to the sampler; the loss then takes its logq correction)
+        self.sas_neg_dist, self.sas_neg_alpha = neg_dist_args(args, "sas", self.sas_loss)
         self.cdtype = compute_dtype(args)
         d = self.hidden
         if d % self.heads:
@@ -144,7 +148,7 @@ class SAS(nn.Module):
         params = [p for _, p in self.named_parameters()]
         return _SASCEFunction.apply(eng, ids, pos, self.training, *params)
 
-    def sampled_ce_loss(self, log_seqs, pos_seqs, cand):
+    def sampled_ce_loss(self, log_seqs, pos_seqs, cand, logq=None):
         """Scalar loss of the sampled softmax over batch-shared candidates (differentiable; available whatever
         sas_loss says).  cand: int64 (K,), ids in [0, V], shared by every position:
 
@@ -154,15 +158,19 @@ class SAS(nn.Module):
             live(r, j) = cand_j != 0 and cand_j != pos_r       id 0 = an ignored slot; accidental hits masked
             loss  = (1 / max(n, 1)) * sum_valid r [ log(exp(z_r0) + sum_{live j} exp(z_rj)) - z_r0 ],   n = #valid
 
-        Duplicate candidates count separately; there is no logQ correction; with cand = arange(1, V + 1) it is
+        Duplicate candidates count separately; with cand = arange(1, V + 1) it is
         ce_loss up to the padding class 0 (logit exactly 0), which ce_loss counts and no candidate list can name.
         A row with no live candidate, and a batch with no valid row, give loss 0 and zero gradients; row 0 of the
-        item table gets no gradient.  Call backward() before the next loss call."""
+        item table gets no gradient.  Call backward() before the next loss call.
+
+        logq: fp32 (V + 1,) on the device, the log of the distribution the candidates were drawn from
+        (ItemProposal.logq): the logQ correction, z_r0 -= logq[pos_r] and z_rj -= logq[cand_j].  It is a constant
+        of the loss (no gradient); entry 0 is never read.  None: no correction."""
         eng = self.engine()
         dev = self._flat.device
         ids, pos, cand = as_ids(log_seqs, dev), as_ids(pos_seqs, dev), as_ids(cand, dev)
         params = [p for _, p in self.named_parameters()]
-        return _SASSCEFunction.apply(eng, ids, pos, cand, self.training, *params)
+        return _SASSCEFunction.apply(eng, ids, pos, cand, logq, self.training, *params)
 
     def log2feats(self, log_seqs):
         eng = self.engine()
@@ -231,10 +239,10 @@ class _SASCEFunction(torch.autograd.Function):
 
 class _SASSCEFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, engine, ids, pos, cand, training, *params):
+    def forward(ctx, engine, ids, pos, cand, logq, training, *params):
         engine.sync_compute_weights()
         out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
-        ctx.saved = engine.sce_forward(ids, pos, cand, training, out)
+        ctx.saved = engine.sce_forward(ids, pos, cand, training, out, logq=logq)
         ctx.engine = engine
         return out[2].clone()
 
@@ -245,7 +253,7 @@ class _SASSCEFunction(torch.autograd.Function):
         eng.sce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
         ctx.saved = None
         grads = [eng.flat.view(n, grad) for n in eng.flat.names]
-        return (None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, *grads)
 
 
 class SASEngine:
@@ -802,12 +810,13 @@ class SASEngine:
             raise ValueError(f"the sampled-softmax head takes 1 .. {kmax} shared candidates, got {K}")
         return cand
 
-    def sce_forward(self, ids, pos, cand, training, loss_out, max_labelled=None, clone_seed=True):
+    def sce_forward(self, ids, pos, cand, training, loss_out, max_labelled=None, clone_seed=True, logq=None):
         """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and the softmax cross-entropy of
         the positive against the K candidates `cand` (int64 [K], shared by every row; id 0 and a row's own positive
         are masked; SAS.sampled_ce_loss has the definition).  loss_out = {loss sum, valid count, mean}.  Returns the
         saved state for sce_backward.  The sce_* buffers are sized by (cap, K, d) alone; nothing here allocates per
-        step or reads the host."""
+        step or reads the host.  logq (fp32 [V + 1], device): the proposal's correction, subtracted from every logit
+        by the rs_sce_head_logq_* entries (no bias); sce_backward reads it from the saved state."""
         d, dt = self.d, self.dt
         if dt == torch.bfloat16 and d % 8:
             raise ValueError(f"the bf16 sampled-softmax head needs hidden units divisible by 8 (got {d}); "
@@ -815,11 +824,16 @@ class SASEngine:
         if not ops.sas_sce_ok(d, dt):
             raise ValueError(f"the sampled-softmax head covers hidden units up to 1024 (got {d})")
         cand = self._sce_cand(cand)
+        E = self.W("item_emb.weight")
+        logq = check_logq(logq, E)
         _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
         c = self._valid_rows_forward(s, pos, max_labelled)
         ws = self.ws.get("sce_ws", (ops.sas_sce_ws_numel(c["cap"], cand.numel(), d),), torch.float32)
-        ops.sas_sce_fwd(c["hl"], c["lab"], c["cnt"], c["cap"], self.W("item_emb.weight"), cand, c["div"], ws, loss_out)
-        c.update(cand=cand, sce_ws=ws)
+        if logq is None:
+            ops.sas_sce_fwd(c["hl"], c["lab"], c["cnt"], c["cap"], E, cand, c["div"], ws, loss_out)
+        else:                                           # the same workspace: rs_sce_head_ws_bytes without a bias
+            ops.sce_head_fwd(c["hl"], c["lab"], c["cnt"], c["cap"], E, None, cand, c["div"], ws, loss_out, logq=logq)
+        c.update(cand=cand, sce_ws=ws, logq=logq)
         s.update(ce=c)
         return s
 
@@ -840,8 +854,12 @@ class SASEngine:
         sk = ops.sas_sce_dh_splits(cap, K, d)          # one fp32 slab per split of the candidates
         dh, coef = g("sce_dh", (sk, cap, d), f32), g("sce_coef", (cap,), f32)
         src, keys = g("sce_src", (cap + K, d), f32), g("sce_keys", (cap + K,), torch.int64)
-        ops.sas_sce_bwd(hl, lab, cnt, cap, self.W("item_emb.weight"), cand, c["div"], dloss, c["sce_ws"], dh, coef,
-                        src[:cap], src[cap:], keys)
+        if c["logq"] is None:
+            ops.sas_sce_bwd(hl, lab, cnt, cap, self.W("item_emb.weight"), cand, c["div"], dloss, c["sce_ws"], dh, coef,
+                            src[:cap], src[cap:], keys)
+        else:
+            ops.sce_head_bwd(hl, lab, cnt, cap, self.W("item_emb.weight"), None, cand, c["div"], dloss, c["sce_ws"],
+                             dh, coef, src[:cap], src[cap:], None, keys, logq=c["logq"])
         # the index's key range: at least past the counting sort's table limit, so that the radix path is taken and
         # the workspace is sized by the entry count alone (the counting sort's histograms are sized by the table)
         rows = max(GE.shape[0], SCE_INDEX_ROWS)

@@ -935,19 +935,32 @@ def _sce_head_bias(bias, E):
     assert bias is None or (bias.dtype == torch.float32 and bias.shape == (E.shape[0],) and bias.is_contiguous())
 
 
-def sce_head_fwd(hl, lab, count, cap, E, bias, cand, divisor, ws, out):
-    """sas_sce_fwd on the logits <h, E[.]> + bias[.] (bias fp32 [V1] or None): rs_sce_head_fwd."""
+def _sce_head_logq(logq, E):
+    assert logq.dtype == torch.float32 and logq.shape == (E.shape[0],) and logq.is_contiguous()
+    assert logq.device == E.device
+
+
+def sce_head_fwd(hl, lab, count, cap, E, bias, cand, divisor, ws, out, logq=None):
+    """sas_sce_fwd on the logits <h, E[.]> + bias[.] (bias fp32 [V1] or None): rs_sce_head_fwd.  logq (fp32 [V1]):
+    the logits are <h, E[.]> + bias[.] - logq[.], the proposal's correction (rs_sce_head_logq_fwd)."""
     d, K = hl.shape[1], cand.numel()
     assert hl.shape[0] >= cap and lab.numel() >= cap and E.dtype == hl.dtype and E.shape[1] == d and E.is_contiguous()
     assert cand.dtype == torch.int64 and cand.is_contiguous()
     assert ws.numel() >= sce_head_ws_numel(cap, K, d, hl.dtype, bias is not None)
     _sce_head_bias(bias, E)
+    if logq is not None:
+        _sce_head_logq(logq, E)
+        call("rs_sce_head_logq_fwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), ptr(bias),
+             ptr(logq), E.shape[0], ptr(cand), K, ptr(divisor), ptr(ws), ptr(out), stream())
+        return
     call("rs_sce_head_fwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), ptr(bias),
          E.shape[0], ptr(cand), K, ptr(divisor), ptr(ws), ptr(out), stream())
 
 
-def sce_head_bwd(hl, lab, count, cap, E, bias, cand, divisor, dloss, ws, dh, coef, pg, dEc, dbc, keys=None):
-    """sas_sce_bwd's outputs on those logits, and dbc fp32 [K] (with a bias; None without): rs_sce_head_bwd."""
+def sce_head_bwd(hl, lab, count, cap, E, bias, cand, divisor, dloss, ws, dh, coef, pg, dEc, dbc, keys=None,
+                 logq=None):
+    """sas_sce_bwd's outputs on those logits, and dbc fp32 [K] (with a bias; None without): rs_sce_head_bwd.  logq:
+    as in sce_head_fwd (rs_sce_head_logq_bwd); it gets no gradient and does not change what dbc is tied to."""
     d, K = hl.shape[1], cand.numel()
     assert dh.numel() >= sce_head_dh_splits(cap, K, d, hl.dtype) * cap * d and coef.numel() >= cap
     assert pg.numel() >= cap * d and dEc.numel() >= K * d
@@ -956,6 +969,12 @@ def sce_head_bwd(hl, lab, count, cap, E, bias, cand, divisor, dloss, ws, dh, coe
     assert E.shape[1] == d and E.is_contiguous() and E.dtype == hl.dtype
     _sce_head_bias(bias, E)
     assert (dbc is None) == (bias is None) and (dbc is None or (dbc.dtype == torch.float32 and dbc.numel() >= K))
+    if logq is not None:
+        _sce_head_logq(logq, E)
+        call("rs_sce_head_logq_bwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), ptr(bias),
+             ptr(logq), E.shape[0], ptr(cand), K, ptr(divisor), ptr(dloss), ptr(ws), ptr(dh), ptr(coef), ptr(pg),
+             ptr(dEc), ptr(dbc), ptr(keys), stream())
+        return
     call("rs_sce_head_bwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(count), ptr(E), ptr(bias),
          E.shape[0], ptr(cand), K, ptr(divisor), ptr(dloss), ptr(ws), ptr(dh), ptr(coef), ptr(pg), ptr(dEc), ptr(dbc),
          ptr(keys), stream())
@@ -964,6 +983,14 @@ def sce_head_bwd(hl, lab, count, cap, E, bias, cand, divisor, dloss, ws, dh, coe
 def uniform_items(seed_base, salt, item_num, out):
     """out (int64, device): uniform draws with replacement over [1, item_num] from (seed_base, salt)."""
     call("rs_uniform_items", ptr(seed_base), salt, item_num, out.numel(), ptr(out), stream())
+
+
+def alias_items(seed_base, salt, table, out):
+    """out (int64, device): draws with replacement over [1, V] from the packed alias table (int64 [V], device:
+    ItemProposal.table) and (seed_base, salt): rs_alias_items."""
+    assert table.dtype == torch.int64 and table.dim() == 1 and table.is_contiguous() and table.device == out.device
+    assert out.dtype == torch.int64 and out.is_contiguous()
+    call("rs_alias_items", ptr(seed_base), salt, ptr(table), table.numel(), out.numel(), ptr(out), stream())
 
 
 def sas_head_finish(part, divisor, out):

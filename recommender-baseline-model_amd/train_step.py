@@ -156,7 +156,8 @@ class FusedStepLR:
 
 class FusedTrainStep:
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
-                 bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None):
+                 bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None,
+                 logq=None):
         """model: rbm_amd SASModel or BERTModel on a CUDA device.
         dp: data-parallel mode (default: torch.distributed initialised with world size > 1).
         max_labelled (BERT; SAS with loss="ce": the valid rows, pos != 0): upper bound on labelled rows per batch
@@ -170,6 +171,10 @@ class FusedTrainStep:
         default), or "sampled_ce" (the softmax over the label and K candidates shared by the whole batch,
         BERTModel.sampled_ce_loss; the batch is (tokens, labels, cand)): single device, steps_per_graph = 1, no
         vocab_shard.
+        logq (loss="sampled_ce" only): the logQ correction of the sampled softmax, the log of the distribution the
+        candidates are drawn from.  A tensor (fp32, one entry per output row, on the device: ItemProposal.logq): every
+        step subtracts it from the logits.  False: never correct.  None (default): capture_sampled(sampler) adopts
+        sampler.proposal.logq when the sampler draws from a proposal; hand-fed steps run uncorrected.
         overlap (DP, default on unless bucket_numel is given): each gradient bucket's all-reduce starts as soon as the backward has finished it (dp.BucketedExchange);
         bucket_numel: otherwise ONE all-reduce after the backward, in buckets of that many floats.
         vocab_shard (BERT, DP): out.weight / out.bias sharded over the ranks (rbm_amd.vocab_parallel).
@@ -194,6 +199,13 @@ class FusedTrainStep:
             raise ValueError(f"loss={loss!r} needs a SAS model (a BERT step takes loss='sampled_ce', or None for the "
                              "model's own bert_loss: its cross-entropy by default)")
         self.loss = loss
+        if isinstance(logq, torch.Tensor):
+            if loss != "sampled_ce":
+                raise ValueError(f"logq corrects the sampled softmax: it needs loss='sampled_ce' (got loss={loss!r})")
+        elif logq not in (None, False):
+            raise ValueError("logq must be a tensor, False (never correct) or None (adopt the sampler's proposal)")
+        self._logq_arg = logq
+        self.logq = logq if isinstance(logq, torch.Tensor) else None
         dp_on = dpx.world() > 1 if dp is None else bool(dp)
         if loss in ("ce", "sampled_ce") and dp_on:
             raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
@@ -416,7 +428,7 @@ class FusedTrainStep:
         elif self.kind == "sas" and self.loss == "sampled_ce":
             seq, pos, cand = batch
             saved = eng.sce_forward(seq, pos, cand, True, self.loss_out, max_labelled=self.max_labelled,
-                                    clone_seed=False)
+                                    clone_seed=False, logq=self.logq)
             eng.sce_backward(saved, self.flat.grad)
         elif self.kind == "sas":
             seq, pos, neg = batch
@@ -441,7 +453,7 @@ class FusedTrainStep:
         elif self.loss == "sampled_ce":
             tokens, labels, cand = batch
             saved = eng.sce_forward(tokens, labels, cand, True, self.loss_out, max_labelled=self.max_labelled,
-                                    clone_seed=False)
+                                    clone_seed=False, logq=self.logq)
             eng.sce_backward(saved, self.flat.grad)
         else:
             tokens, labels = batch
@@ -995,6 +1007,8 @@ class FusedTrainStep:
             K = getattr(sampler, "shared_negs", None)
             if not K:
                 raise ValueError("loss='sampled_ce' needs a sampler with shared_negs=K")
+            if self._logq_arg is None and getattr(sampler, "proposal", None) is not None:
+                self.logq = sampler.proposal.logq          # the candidates come from it: the loss corrects for it
             # no packed buffer: cand has another shape (replay_packed then goes through replay(), as after capture()
             # with inputs of different shapes)
             self.packed = None

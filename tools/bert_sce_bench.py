@@ -3,7 +3,7 @@
 cross-entropy step (GPU only).
 
     python tools/bert_sce_bench.py [--reps 30] [--rounds 3] [--out profiles/bert_sce_bench.json]
-                                   [--configs cfg3,cfg5] [--ks 256,1024,4096,16384] [--parts head,step]
+                                   [--configs cfg3,cfg5] [--ks 256,1024,4096,16384] [--parts head,step] [--proposal zipf]
 
 bf16, graph replays (median over --reps replays, each between its own pair of HIP events), --rounds interleaved
 rounds, one JSON line per shape (cfg3: V 26,744; cfg5: V 1,000,000; both B 64, T 200, d 256, 4 blocks, 2 heads,
@@ -14,6 +14,10 @@ dropout 0.1, labelled-row cap 1,792):
   * step: ms/step of the captured fused step with loss="sampled_ce" at every K and with the default cross-entropy,
     the device time of the sampled step's index launches, and the bytes of the engine's sce_* buffers beside the CE
     step's (cap, V + 1) dlogits.
+--proposal zipf adds the popularity leg: the candidates come from an ItemProposal over Zipf(1) weights
+(rs_alias_items), "sweep_bias_logq_fwd" / "_bwd" are the head's launches with its logq beside the bias
+(rs_sce_head_logq_*), "logq_step_ms_k{K}" the step without and with it captured in turn on one step object
+(sas_sce_bench.toggled_step_ms), "alias_items" / "uniform_items" the samplers' launches.
 No pass / fail.
 """
 import argparse
@@ -31,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import rbm_amd  # noqa: E402,F401
 import rbm_amd.data as synth  # noqa: E402
 from rbm_amd import ops  # noqa: E402
+from rbm_amd.dataloaders import ItemProposal  # noqa: E402
 from rbm_amd.models import model_factory  # noqa: E402
 from rbm_amd.train_step import FusedTrainStep  # noqa: E402
 from sas_ce_bench import launch_us, replay_us  # noqa: E402
@@ -51,7 +56,11 @@ def model(cfg, seed=0):
     return m
 
 
-def head_alone(cfg, ks, reps, rounds):
+def zipf_proposal(V):
+    return ItemProposal(np.concatenate([[0.0], 1.0 / np.arange(1, V + 1)]))
+
+
+def head_alone(cfg, ks, reps, rounds, prop=None):
     """The head's launches on random rows: cap valid rows of width d against a [V + 1][d] table."""
     V, d, cap = cfg["V"], cfg["d"], cfg["cap"]
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -65,6 +74,9 @@ def head_alone(cfg, ks, reps, rounds):
     r = {}
     for K in ks:
         cand = torch.randint(1, V + 1, (K,), device="cuda", generator=g)
+        sb = torch.ones(1, dtype=torch.int64, device="cuda")
+        if prop is not None:
+            ops.alias_items(sb, K, prop.table, cand)
         sk = ops.sce_head_dh_splits(cap, K, d, BF)
         ws = torch.zeros(ops.sce_head_ws_numel(cap, K, d, BF, True), device="cuda")
         dh, coef = torch.zeros(sk, cap, d, device="cuda"), torch.zeros(cap, device="cuda")
@@ -81,6 +93,14 @@ def head_alone(cfg, ks, reps, rounds):
             "sweep_bias_bwd": lambda: ops.sce_head_bwd(hl, lab, cnt, cap, E, bias, cand, div, None, ws, dh, coef,
                                                        src[:cap], src[cap:], dbc, keys),
         }
+        if prop is not None:
+            q, draws = prop.logq, torch.empty_like(cand)
+            fns.update({
+                "sweep_bias_logq_fwd": lambda: ops.sce_head_fwd(hl, lab, cnt, cap, E, bias, cand, div, ws, out, logq=q),
+                "sweep_bias_logq_bwd": lambda: ops.sce_head_bwd(hl, lab, cnt, cap, E, bias, cand, div, None, ws, dh,
+                                                                coef, src[:cap], src[cap:], dbc, keys, logq=q),
+                "alias_items": lambda: ops.alias_items(sb, 7, prop.table, draws),
+                "uniform_items": lambda: ops.uniform_items(sb, 7, V, draws)})
         us = {k: [] for k in fns}
         for _ in range(rounds):
             for k, fn in fns.items():
@@ -92,13 +112,16 @@ def head_alone(cfg, ks, reps, rounds):
     return r
 
 
-def whole_step(cfg, ks, reps, rounds):
+def whole_step(cfg, ks, reps, rounds, prop=None):
     rng = np.random.default_rng(0)
     zipf = synth.ZipfItems(cfg["V"])
     batch = [torch.from_numpy(x).cuda() for x in
              synth.bert_batch(rng, cfg["B"], cfg["T"], cfg["V"], mask_prob=cfg["mask"], shape=cfg["shape"], zipf=zipf)]
     assert int((batch[1] != 0).sum()) <= cfg["cap"]
     cands = {K: torch.from_numpy(rng.integers(1, cfg["V"] + 1, K)).cuda() for K in ks}
+    if prop is not None:
+        for K in ks:
+            ops.alias_items(torch.ones(1, dtype=torch.int64, device="cuda"), K, prop.table, cands[K])
     steps = {"ce": FusedTrainStep(model(cfg), lr=1e-3, max_labelled=cfg["cap"]).capture(*batch, warmup=3)}
     for K in ks:
         steps[f"sampled_ce_k{K}"] = FusedTrainStep(model(cfg), lr=1e-3, max_labelled=cfg["cap"],
@@ -134,6 +157,11 @@ def whole_step(cfg, ks, reps, rounds):
     # the optimizer alone (the two 1M-row tables dominate it at cfg5): its share of the sampled step
     t = steps[f"sampled_ce_k{ks[0]}"]
     r["adam_us"] = launch_us(lambda: t._update(), reps)
+    if prop is not None:
+        from sas_sce_bench import toggled_step_ms
+        for K in ks:
+            r[f"logq_step_ms_k{K}"] = toggled_step_ms(steps[f"sampled_ce_k{K}"], (*batch, cands[K]), prop.logq, reps,
+                                                      rounds)
     return r
 
 
@@ -145,6 +173,7 @@ def main():
     ap.add_argument("--configs", default="cfg3,cfg5")
     ap.add_argument("--ks", default="256,1024,4096,16384")
     ap.add_argument("--parts", default="head,step")
+    ap.add_argument("--proposal", default="", choices=["", "zipf"])
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bert_sce_bench needs a GPU"
     ks = [int(k) for k in a.ks.split(",")]
@@ -152,11 +181,12 @@ def main():
     for name in a.configs.split(","):
         cfg = CONFIGS[name]
         r = {"config": name, **{k: cfg[k] for k in ("B", "T", "V", "d", "L", "cap", "p")}, "dtype": "bf16",
-             "reps": a.reps, "rounds": a.rounds}
+             "reps": a.reps, "rounds": a.rounds, "proposal": a.proposal or "uniform"}
+        prop = zipf_proposal(cfg["V"]) if a.proposal else None
         if "head" in a.parts:
-            r["head"] = head_alone(cfg, ks, a.reps, a.rounds)
+            r["head"] = head_alone(cfg, ks, a.reps, a.rounds, prop)
         if "step" in a.parts:
-            r["step"] = whole_step(cfg, ks, a.reps, a.rounds)
+            r["step"] = whole_step(cfg, ks, a.reps, a.rounds, prop)
         lines.append(json.dumps(r))
         print(lines[-1], flush=True)
         torch.cuda.empty_cache()
