@@ -626,6 +626,31 @@ int rs_rows_pack(const float* src, int64_t rows, int64_t d, const int32_t* index
                  float* compact, int64_t cap, void* stream);
 int rs_rows_unpack(float* dst, int64_t rows, int64_t d, const int32_t* index, const float* compact, void* stream);
 
+/* Sparse (touched-rows-only) Adam of an embedding / output table (adam_rows.hip): the lazy rule of torch's
+ * SparseAdam / TensorFlow's LazyAdam in the dense sweep's arithmetic -- the reference's optimizer is the dense
+ * torch.optim.Adam (BS/trainers/base.py:225-228), which rs_adam_step replaces; this one is an opt-in for sampled
+ * losses whose step touches few rows of a large table.
+ * rs_unique_rows: rows[0 .. *count) = the distinct keys in [1, table_rows) of up to three int64 key arrays (keysK
+ * may be NULL when nK == 0), ascending; keys of 0 or >= table_rows (or negative) are dropped; entries past *count
+ * are unspecified.  cap (the capacity of rows[]) >= n0 + n1 + n2.  ws: rs_unique_rows_ws_bytes(table_rows) =
+ * 4 * (table_rows + 2 * ceil(table_rows / 2048)) bytes, 4-byte aligned -- ints per table row, nothing per row
+ * element; needs no initialisation.  No host synchronisation (graph-capturable), no atomics: the same key set gives
+ * the same list.  table_rows < 2^31.
+ * rs_adam_rows: for i < min(*count, cap), row r = rows[i] of the table whose row 0 p / g / m / v / p_bf16 point at
+ * (d fp32 per row; p_bf16 NULL in fp32 mode) gets rs_adam_step's per-element update with the step's scalars in
+ * state[1..3] -- so it runs after the step's rs_adam_prepare / rs_adam_prepare_step launch on the same stream -- and
+ * its gradient is cleared when zero_grad; bit for bit what rs_adam_step gives on those rows.  Every other row is
+ * neither read nor written.  A row id outside [0, table_rows) is skipped; the listed ids must be distinct.  16-byte
+ * accesses when d % 4 == 0 and the bases are 16-byte (p_bf16: 8-byte) aligned, else element by element (d = 50,
+ * d = 1).  At most max_wg workgroups, grid-stride over the list; cap * d < 2^31. */
+int64_t rs_unique_rows_ws_bytes(int64_t table_rows);
+int rs_unique_rows(const int64_t* keys0, int64_t n0, const int64_t* keys1, int64_t n1, const int64_t* keys2,
+                   int64_t n2, int64_t table_rows, int32_t* rows, int32_t* count, int64_t cap, void* ws,
+                   int64_t ws_bytes, void* stream);
+int rs_adam_rows(int64_t d, int64_t table_rows, const int32_t* rows, const int32_t* count, int64_t cap, float* p,
+                 float* g, float* m, float* v, void* p_bf16, const double* state, const double* hyper, int zero_grad,
+                 int max_wg, void* stream);
+
 /* Batched bf16 transpose: for m < nmat, desc[6m..6m+5] = {rows, cols, src_off, lds, dst_off, ldd}
  * (elements): dst[dst_off + c*ldd + r] = src[src_off + r*lds + c].  Grid x = max_tiles >= the
  * largest ceil(rows/64)*ceil(cols/64). */

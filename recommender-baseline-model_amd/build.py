@@ -24,7 +24,7 @@ ARCH = os.environ.get("RS_OFFLOAD_ARCH", "gfx950")
 # objects, and a unit inserted in the middle moves every later one: with sas_ce.hip at its alphabetical place the
 # cfg2 BCE step (which launches nothing of it) measured 0.2763 ms against 0.2748 before the unit existed and 0.2737
 # with it linked last (means of six interleaved bench.py runs each).  New units go here.
-LINK_LAST = ("sas_ce.hip", "sas_sce.hip")
+LINK_LAST = ("sas_ce.hip", "sas_sce.hip", "adam_rows.hip")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -60,7 +60,8 @@ def build(force=False, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
     # sources marked "rs-build: included" on line 1 are compiled inside the file that includes them
     srcs = [p for p in sorted(glob.glob(os.path.join(CSRC, "*.hip"))) if not _included(p)]
-    srcs.sort(key=lambda p: os.path.basename(p) in LINK_LAST)      # stable: the rest stay alphabetical
+    # stable: the rest stay alphabetical, the LINK_LAST units follow in the order listed there
+    srcs.sort(key=lambda p: LINK_LAST.index(os.path.basename(p)) + 1 if os.path.basename(p) in LINK_LAST else 0)
     jobs = jobs or min(len(srcs), max(1, min(8, os.cpu_count() or 1)))
     with cf.ThreadPoolExecutor(jobs) as ex:
         results = list(ex.map(lambda s: _compile(s, force), srcs))

@@ -673,6 +673,72 @@ def rows_unpack(dst, index, compact):
     call("rs_rows_unpack", ptr(dst), rows, d, ptr(index), ptr(compact), stream())
 
 
+# ---- sparse (touched-rows-only) Adam of a table (adam_rows.hip) ------------------------------
+def unique_rows_ws_bytes(table_rows):
+    n = int(_lib.lib().rs_unique_rows_ws_bytes(int(table_rows)))
+    if n < 0:
+        raise ValueError("rs_unique_rows_ws_bytes: table_rows must be positive")
+    return n
+
+
+def _i32(t, name, numel=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous int32 tensor")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name} must hold {numel} element(s), got {t.numel()}")
+
+
+def unique_rows(keys, table_rows, rows, count, ws):
+    """rows[:count] (int32 [cap], count int32 [1], both on the device; no sync) = the ascending distinct ids in
+    [1, table_rows) of the one to three int64 key tensors `keys`; ids of 0 or >= table_rows are dropped, entries past
+    count are unspecified.  cap >= the keys' total length; ws: uint8 [unique_rows_ws_bytes(table_rows)]."""
+    keys = list(keys)
+    if not 1 <= len(keys) <= 3:
+        raise ValueError(f"unique_rows takes one to three key tensors, got {len(keys)}")
+    for k in keys:
+        if not isinstance(k, torch.Tensor) or k.dtype != torch.int64 or not k.is_contiguous():
+            raise ValueError("unique_rows: every key tensor must be contiguous int64")
+    table_rows = int(table_rows)
+    if not 0 < table_rows < 2 ** 31:
+        raise ValueError(f"unique_rows: table_rows must be in [1, 2^31), got {table_rows}")
+    _i32(rows, "rows")
+    _i32(count, "count", 1)
+    total = sum(k.numel() for k in keys)
+    if rows.numel() < max(total, 1):
+        raise ValueError(f"unique_rows: rows holds {rows.numel()} ids but the keys number {total}")
+    if ws.dtype != torch.uint8 or ws.numel() < unique_rows_ws_bytes(table_rows):
+        raise ValueError(f"unique_rows: ws must be uint8 with at least {unique_rows_ws_bytes(table_rows)} bytes")
+    kp = [(ptr(k) if k.numel() else None, k.numel()) for k in keys] + [(None, 0)] * (3 - len(keys))
+    call("rs_unique_rows", kp[0][0], kp[0][1], kp[1][0], kp[1][1], kp[2][0], kp[2][1], table_rows, ptr(rows),
+         ptr(count), rows.numel(), ptr(ws), ws.numel(), stream())
+
+
+def adam_rows(rows, count, p, g, m, v, p_bf16, state, hyper, zero_grad=False, max_wg=None):
+    """rs_adam_step's update on the rows rows[:count] (unique_rows' list: distinct ids) of the table p / g / m / v
+    (fp32 [R, d] or [R], contiguous views of the flat buffers; p_bf16 its bf16 copy or None) and on no other row.
+    The step's scalars must be prepared (after adam_prepare / adam_prepare_step of this step, same stream)."""
+    _i32(rows, "rows")
+    _i32(count, "count", 1)
+    if p.dim() not in (1, 2):
+        raise ValueError("adam_rows: the table must be [R, d] or [R]")
+    R, d = p.shape[0], (p.shape[1] if p.dim() == 2 else 1)
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or t.shape != p.shape or not t.is_contiguous():
+            raise ValueError(f"adam_rows: {name} must be contiguous fp32 of the table's shape {tuple(p.shape)}")
+    if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.shape != p.shape or not p_bf16.is_contiguous()):
+        raise ValueError("adam_rows: p_bf16 must be a contiguous bf16 tensor of the table's shape")
+    if R < 1 or d < 1 or rows.numel() < 1:
+        raise ValueError("adam_rows: empty table or list")
+    if rows.numel() * d >= 2 ** 31:
+        raise ValueError("adam_rows: list capacity * row width must stay below 2^31")
+    if max_wg is not None and int(max_wg) < 1:
+        raise ValueError("adam_rows: max_wg must be positive")
+    if state.dtype != torch.float64 or state.numel() < 4 or hyper.dtype != torch.float64 or hyper.numel() < 5:
+        raise ValueError("adam_rows: state / hyper must be the optimizer's float64 device arrays")
+    call("rs_adam_rows", d, R, ptr(rows), ptr(count), rows.numel(), ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16),
+         ptr(state), ptr(hyper), int(zero_grad), int(max_wg or 8192), stream())
+
+
 def ln_partial_segments(part, M, d, dgamma, dbeta, nb=None):
     """The two reduce segments of a fused kernel's LayerNorm partials (part[b][2][d], b < nb; default: the
     SAS row-block backward kernels' set count)."""

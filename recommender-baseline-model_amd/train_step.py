@@ -29,6 +29,7 @@ import torch
 from . import dp as dpx
 from . import ops
 from .engine_util import SideBranch, release_capture_events
+from .flat import ALIGN
 
 
 # thread-local capture: the process group's watchdog thread polls its collectives' events while a step graph is
@@ -48,6 +49,7 @@ class FusedAdam:
         # state[16 + 16 k], k < 8)]
         self.state = torch.zeros(144, dtype=torch.float64, device=dev)
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float64, device=dev)
+        self.weight_decay = float(weight_decay)     # host copy: step(sparse=...) refuses a non-zero decay
         # (table lo, rows, log2 d, row marks, epoch): a table whose gradient rows only the marked item gradient
         # writes -- the sweep skips the gradient loads of the rows it did not stamp (rs_adam_*_marked)
         self.marks = None
@@ -64,7 +66,31 @@ class FusedAdam:
         """StepLR hook (BS/trainers/base.py:40,87): lives on the device, so graph replays see it."""
         self.hyper[0] = lr
 
-    def step(self, grad_divisor=None, seed_base=None, ranges=None, transposed=None, loss=None, keep=None):
+    def _sparse_segments(self, sparse):
+        """The dense launches' ranges beside the sparse tables: the complement of the tables in the flat buffer.  A
+        table's range runs to the end of its alignment padding (FlatParams.ALIGN), whose elements are zero in every
+        buffer and stay so under either rule, so each dense range starts 16-byte aligned."""
+        f = self.flat
+        if self.weight_decay != 0.0:
+            raise ValueError("sparse tables need weight_decay == 0: the decay has no meaning for a skipped row")
+        cuts = []
+        for lo, rows, d, lst, cnt in sparse:
+            lo, n = int(lo), int(rows) * int(d)
+            if lo % ALIGN or lo < 0 or n <= 0 or lo + n > f.numel:
+                raise ValueError(f"sparse table (lo={lo}, rows={rows}, d={d}) is not a parameter of the flat buffer")
+            cuts.append((lo, min(lo + -(-n // ALIGN) * ALIGN, f.numel)))
+        cuts.sort()
+        segs, a = [], 0
+        for lo, hi in cuts + [(f.numel, f.numel)]:
+            if lo < a:
+                raise ValueError("sparse tables overlap")
+            if lo > a:
+                segs.append((a, lo, True))
+            a = hi
+        return segs
+
+    def step(self, grad_divisor=None, seed_base=None, ranges=None, transposed=None, loss=None, keep=None,
+             sparse=None):
         """One Adam update; also clears the gradient buffer (the next step accumulates from zero) and
         advances the dropout step seed when given.  ranges: [(lo, hi)] flat slices to update (default all; a
         vocabulary-sharded rank skips the output rows other ranks own).  loss = (sum, out): out = sum / grad_divisor
@@ -72,9 +98,26 @@ class FusedAdam:
         launch, which must cover those matrices.  keep = (lo, hi): a slice the backward OVERWRITES every step
         (BERT's out.weight / out.bias with a large vocabulary): updated by its own launch that leaves its gradient
         in place -- no zero written by this sweep, none read back by the next step's dE GEMM (2 GB per step at 1M
-        items)."""
+        items).
+
+        sparse = [(lo, rows, d, rows_list, count)]: tables [rows][d] at flat offset lo that take the LAZY rule: only
+        the rows rows_list[:count] (ops.unique_rows: int32 device list and count, distinct ids) are updated, by
+        rs_adam_rows after the preparing launch, with the dense sweep's arithmetic and this step's scalars (one
+        global step count, advanced once); every other row of p / m / v / the bf16 copy stays bit for bit, and its
+        gradient (zero by contract) is neither read nor written.  The dense launches cover the rest of the buffer.
+        With every row listed every step this equals the dense step bit for bit.  Against torch.optim.SparseAdam
+        the rule differs only in where eps sits: the dense kernel's denom = sqrt(v) / sqrt(bc2) + eps with step size
+        lr / bc1 is kept, where SparseAdam forms sqrt(v) + eps and folds sqrt(bc2) into the step size.  Needs
+        weight_decay == 0 (ValueError), and neither ranges nor keep."""
         f = self.flat
-        segs = [(lo, hi, True) for lo, hi in (ranges or [(0, f.numel)])]
+        if sparse:
+            if ranges is not None or keep is not None:
+                raise ValueError("sparse tables go with neither ranges nor keep")
+            segs = self._sparse_segments(sparse)
+            if not segs:     # nothing dense: the step's scalars by their own launch
+                ops.adam_prepare(self.state, self.hyper, grad_divisor, seed_base)
+        else:
+            segs = [(lo, hi, True) for lo, hi in (ranges or [(0, f.numel)])]
         if keep is not None and ranges is None:
             klo, khi = keep
             assert 0 < klo < khi <= f.numel and klo % 4 == 0 and khi % 4 == 0, keep
@@ -90,7 +133,12 @@ class FusedAdam:
             else:
                 ops.adam_step(f.data[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], bf, self.state,
                               self.hyper, zero_grad=zg, marks=self._marks(lo, hi))
-
+        for lo, rows, d, lst, cnt in sparse or ():
+            hi = lo + rows * d
+            shp = (rows, d) if d > 1 else (rows,)
+            bf = f.bf16[lo:hi].view(shp) if f.bf16 is not None else None
+            ops.adam_rows(lst, cnt, f.data[lo:hi].view(shp), f.grad[lo:hi].view(shp), self.m[lo:hi].view(shp),
+                          self.v[lo:hi].view(shp), bf, self.state, self.hyper, zero_grad=True)
 
     def step_keep_early(self, keep, max_wg=None, zero_grad=False):
         """The first part of a step whose `keep` range is final before the rest of the backward (BERT's out.weight /
@@ -157,8 +205,18 @@ class FusedStepLR:
 class FusedTrainStep:
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
                  bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None,
-                 logq=None):
+                 logq=None, table_optim="dense"):
         """model: rbm_amd SASModel or BERTModel on a CUDA device.
+        table_optim: "dense" (default: the reference's torch.optim.Adam on every parameter, bit for bit) or "sparse":
+        the embedding / output tables of a sampled loss take the lazy rule (FusedAdam.step(sparse=...): rows without
+        a gradient this step are left alone, as torch's SparseAdam / TensorFlow's LazyAdam do), so the optimizer's
+        cost follows the batch and the candidate count, not the catalogue.  Covered: SAS loss="bce" / "sampled_ce"
+        (item_emb.weight) and BERT loss="sampled_ce" (the token table, out.weight and out.bias); one device, no
+        vocab_shard, weight_decay == 0 and l2_emb == 0, else ValueError.  A row is touched iff its id occurs,
+        non-zero, in the keys of one of the step's item-index builds: SAS bce seq | pos | neg; SAS sampled_ce
+        seq | pos | cand; BERT sampled_ce tokens for the token table, labels | cand for out.weight and out.bias (one
+        list for both).  Checkpoints keep their format; resuming such a run in torch's dense Adam is legal and
+        continues densely (untouched rows then decay again).
         dp: data-parallel mode (default: torch.distributed initialised with world size > 1).
         max_labelled (BERT; SAS with loss="ce": the valid rows, pos != 0): upper bound on labelled rows per batch
         (sizes the compacted vocabulary-logit buffers; default B*T).
@@ -207,6 +265,26 @@ class FusedTrainStep:
         self._logq_arg = logq
         self.logq = logq if isinstance(logq, torch.Tensor) else None
         dp_on = dpx.world() > 1 if dp is None else bool(dp)
+        if table_optim not in ("dense", "sparse"):
+            raise ValueError(f"table_optim must be 'dense' or 'sparse', got {table_optim!r}")
+        self.table_optim = table_optim
+        if table_optim == "sparse":      # every refusal before the first launch
+            why = None
+            if self.kind == "sas" and loss == "ce":
+                why = "loss='ce' gives every row of the item table a gradient: there is nothing to skip"
+            elif self.kind == "bert" and loss != "sampled_ce":
+                why = ("BERT's full cross-entropy writes a dense out.weight / out.bias gradient (and takes the "
+                       "keep / early-head optimizer path): only loss='sampled_ce' is covered")
+            elif dp_on:
+                why = "it runs on one rank (the data-parallel gradient exchange is not covered)"
+            elif vocab_shard:
+                why = "vocab_shard is not covered"
+            elif weight_decay != 0.0:
+                why = f"weight_decay must be 0 (got {weight_decay}): the decay has no meaning for a skipped row"
+            elif self.kind == "sas" and float(getattr(model.sas, "l2_emb", 0.0)) != 0.0:
+                why = f"l2_emb must be 0 (got {model.sas.l2_emb}): the regulariser gives every row a gradient"
+            if why:
+                raise ValueError(f"FusedTrainStep(table_optim='sparse'): {why}")
         if loss in ("ce", "sampled_ce") and dp_on:
             raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
         if self.kind == "bert" and loss == "sampled_ce" and vocab_shard:
@@ -323,9 +401,28 @@ class FusedTrainStep:
         # (SAS: its head rows land in the marked table itself.  BERT's sampled head writes out.weight / out.bias, not the
         # marked token table, whose rows still come from the stamping launch alone: the marks stay on.)
         tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce")
-        if tied_head:
+        # A sparse table takes no marks either: its untouched rows are not swept at all.
+        sparse = table_optim == "sparse"
+        if tied_head or sparse:
             self.engine.row_marks = None
-        if (not self.dp and not self.l2 and not tied_head
+        # sparse tables: [(key positions in the batch, [(flat offset, rows, d)])] -- one union list per entry, shared
+        # by its tables (out.weight and out.bias); the lists and their workspaces are allocated by the first step
+        self._sparse_tables = None
+        self._sparse_bufs = None
+        self._rows_side = None
+        if sparse:
+            f = self.flat
+
+            def tab(name):
+                shp = f.shapes[name]
+                return (f.offsets[name], shp[0], shp[1] if len(shp) > 1 else 1)
+            if self.kind == "sas":      # bce: seq | pos | neg; sampled_ce: seq | pos | cand
+                self._sparse_tables = [((0, 1, 2), [tab("item_emb.weight")])]
+            else:                       # tokens; labels | cand
+                self._sparse_tables = [((0,), [tab("bert.embedding.token.weight")]),
+                                       ((1, 2), [tab("out.weight"), tab("out.bias")])]
+            self._rows_side = SideBranch(dev, avoid=taken + [self._capture_side.stream])
+        if (not self.dp and not self.l2 and not tied_head and not sparse
                 and os.environ.get("RS_ROW_MARKS", "1") != "0"
                 and hasattr(self.engine, "enable_row_marks")):
             r = self.engine.enable_row_marks(self.ROW_MARKS_MIN)
@@ -382,6 +479,13 @@ class FusedTrainStep:
     def _compute(self, *batch, split=None, update=False):
         # the early optimizer hooks are live only inside this trainer's own steps, whose _update joins them
         # (update=True); a bare forward + backward (tests reading the gradient, the engine driven directly) runs none
+        if self._sparse_tables is not None and update:
+            # the touched-row lists need the batch's keys alone: forked here, before the first launch of the step,
+            # issued after the backward's launches (SideBranch, rule 2), joined by _update before the optimizer
+            fork = self._rows_side.mark()
+            out = self._compute_impl(*batch, split=split)
+            self._build_row_lists(batch, fork)
+            return out
         if not (self._early_ok and update):
             return self._compute_impl(*batch, split=split)
         self.engine.after_head_grads = self._early_head_update
@@ -399,6 +503,36 @@ class FusedTrainStep:
                 # next step's _update to join
                 self._early_forked = False
                 self._early_done = []
+
+    def _build_row_lists(self, batch, fork):
+        """table_optim="sparse": one ops.unique_rows per union list over the batch's key tensors, on the trainer's
+        rows branch ordered after `fork`.  The buffers (list, count, flag workspace per list) are allocated at the
+        first step, sized by the keys' total length and the table's rows."""
+        keys = [[batch[i].reshape(-1) for i in pos] for pos, _ in self._sparse_tables]
+        keys = [[k if k.is_contiguous() else k.contiguous() for k in ks] for ks in keys]
+        sizes = [sum(k.numel() for k in ks) for ks in keys]
+        if self._sparse_bufs is None or [b[0].numel() for b in self._sparse_bufs] != sizes:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the touched-row lists must be allocated by an eager step before a capture")
+            dev = self.flat.device
+            self._sparse_bufs = [(torch.zeros(n, dtype=torch.int32, device=dev),
+                                  torch.zeros(1, dtype=torch.int32, device=dev),
+                                  torch.empty(ops.unique_rows_ws_bytes(tabs[0][1]), dtype=torch.uint8, device=dev))
+                                 for n, (_, tabs) in zip(sizes, self._sparse_tables)]
+        with self._rows_side.run(after=fork):
+            for ks, (_, tabs), (lst, cnt, ws) in zip(keys, self._sparse_tables, self._sparse_bufs):
+                ops.unique_rows(ks, tabs[0][1], lst, cnt, ws)
+        self._rows_forked = True
+
+    def _sparse_spec(self):
+        """FusedAdam.step's `sparse` for this step: joins the rows branch first."""
+        if not getattr(self, "_rows_forked", False):
+            raise RuntimeError("table_optim='sparse': the optimizer needs the step's touched-row lists (_compute "
+                               "with update=True builds them)")
+        self._rows_side.join()
+        self._rows_forked = False
+        return [(lo, rows, d, lst, cnt) for (_, tabs), (lst, cnt, _) in zip(self._sparse_tables, self._sparse_bufs)
+                for lo, rows, d in tabs]
 
     def _compute_impl(self, *batch, split=None):
         """Forward + loss + backward into the flat gradient.  split(tag): called by the engine when the bucket
@@ -525,7 +659,8 @@ class FusedTrainStep:
                 self._early_forked = False
             else:
                 self._l2(self.loss_out[2:3])
-                self.opt.step(seed_base=sb, transposed=tr, keep=kp)
+                sp = self._sparse_spec() if self._sparse_tables is not None else None
+                self.opt.step(seed_base=sb, transposed=tr, keep=kp, sparse=sp)
 
     def _post_update(self):
         """Sharded item table: all-gather the updated compute rows; the other ranks' master rows are stale now."""
@@ -663,6 +798,10 @@ class FusedTrainStep:
     def load_optimizer_state_dict(self, sd):
         """Resume from a torch.optim.Adam state_dict (e.g. a reference checkpoint's 'optimizer_state_dict')."""
         g = sd["param_groups"][0]
+        if self.table_optim == "sparse" and g["weight_decay"] != 0:
+            raise ValueError("table_optim='sparse' needs weight_decay == 0 (the loaded optimizer state has "
+                             f"{g['weight_decay']})")
+        self.opt.weight_decay = float(g["weight_decay"])
         self.opt.hyper.copy_(torch.tensor([g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]],
                                           dtype=torch.float64))
         slices = self._param_slices()
