@@ -651,6 +651,33 @@ int rs_adam_rows(int64_t d, int64_t table_rows, const int32_t* rows, const int32
                  float* g, float* m, float* v, void* p_bf16, const double* state, const double* hyper, int zero_grad,
                  int max_wg, void* stream);
 
+/* torch.optim.SGD step (sgd.hip): the reference trainer's other optimizer, BS/trainers/base.py:229-233
+ * (args.optimizer == "SGD": optim.SGD(params, lr, weight_decay=args.weight_decay, momentum=args.momentum); dampening
+ * 0, nesterov False), over n elements of a flat fp32 buffer, one launch.  hyper (device double[3]) = {lr, momentum,
+ * weight_decay}: doubles as torch's Python floats, cast to float where they meet the tensors.  Per element, every
+ * rounding as torch's float32 kernels place it (sgd_math.h):
+ *     gj = (gs == 1) ? g : g * gs                  gs = 1 / *grad_divisor (data parallel), 1 when it is NULL
+ *     if (wd != 0) gj = fma(wd, p, gj)             grad.add(param, alpha=weight_decay)
+ *     if (buf)     b  = (b * momentum) + gj        buf.mul_(momentum).add_(grad): two roundings, no fma
+ *                  p  = fma(-lr, buf ? b : gj, p)  param.add_(buf, alpha=-lr)
+ * A zero-initialised buf gives torch's first-step rule (buf = grad.clone()) from the same line.  With gs == 1 the
+ * result equals torch's CPU float32 SGD bit for bit.
+ * buf == NULL: the momentum-free form -- no buffer is read or written and hyper[1] is ignored.  p_bf16 (NULL in fp32
+ * mode) receives bf16(p); zero_grad != 0 clears g (stores only where it is not zero already).  ntd > 0: the bf16
+ * result is also written transposed, tdesc / tbase / wT as rs_adam_prepare_step's (lds % 4 == 0, every matrix inside
+ * [tbase, tbase + n / 4 * 4), rows * lds < 2^31: the caller's promise).  At most max_wg workgroups, grid-stride
+ * (0 = one float4 per thread, unbounded); every grid gives the same bits.
+ * prepare != 0 marks the first range of a step: that launch also does state[0] += 1 (state: device double[>= 1], the
+ * step count kernel stamps and checkpoints read), *seed_base += 1 when given (the next step's dropout masks), and
+ * *loss_out = *loss_sum / *grad_divisor when given.  Nothing in the kernel reads those three, so further ranges of
+ * the step (prepare == 0) may follow in any order on the same stream.  Every launch reads grad_divisor itself.
+ * RS_ERR_ARG before any launch: n <= 0; NULL p, g, state or hyper; p, g or buf not 16-byte (p_bf16: 8-byte) aligned;
+ * ntd < 0, or ntd > 0 without p_bf16, tdesc and wT; loss_out without loss_sum and grad_divisor; max_wg < 0.
+ * No allocation, no synchronisation, no atomics: graph-capturable and deterministic. */
+int rs_sgd_step(int64_t n, float* p, float* g, float* buf, void* p_bf16, double* state, const double* hyper,
+                int zero_grad, int prepare, const float* grad_divisor, uint64_t* seed_base, const int64_t* tdesc,
+                int ntd, int64_t tbase, void* wT, const float* loss_sum, float* loss_out, int max_wg, void* stream);
+
 /* Batched bf16 transpose: for m < nmat, desc[6m..6m+5] = {rows, cols, src_off, lds, dst_off, ldd}
  * (elements): dst[dst_off + c*ldd + r] = src[src_off + r*lds + c].  Grid x = max_tiles >= the
  * largest ceil(rows/64)*ceil(cols/64). */

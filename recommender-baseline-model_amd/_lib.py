@@ -154,6 +154,7 @@ SIGNATURES = {
     "rs_unique_rows_ws_bytes": [i64],
     "rs_unique_rows": [vp, i64, vp, i64, vp, i64, i64, vp, vp, i64, vp, i64, vp],
     "rs_adam_rows": [i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
+    "rs_sgd_step": [i64, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, i32, vp],
     "rs_sas_block_grid": [i64],
     "rs_sas_block_boundary_fused": [i64, i64],
     "rs_sas_block_in": [i64, C.POINTER(SasInArgs), vp],

@@ -391,6 +391,35 @@ def adam_prepare_step(p, g, m, v, p_bf16, state, hyper, zero_grad=False, grad_di
          int(zero_grad), ptr(grad_divisor), ptr(seed_base), ptr(td), nt, int(tbase), ptr(wt), stream())
 
 
+def sgd_step(p, g, buf, p_bf16, state, hyper, zero_grad=False, prepare=False, grad_divisor=None, seed_base=None,
+             transposed=None, tbase=0, loss_sum=None, loss_out=None, max_wg=8192):
+    """torch.optim.SGD over a flat range in one launch (rs_sgd_step).  buf None: no momentum.  hyper: double[3] =
+    {lr, momentum, weight_decay} on the device; state: double[>= 1], state[0] the step count.  prepare: the first
+    range of a step (step count, seed, loss_out = loss_sum / grad_divisor).  transposed / tbase: as
+    adam_prepare_step's.  max_wg: at most that many workgroups (0: unbounded)."""
+    if hyper.dtype != torch.float64 or state.dtype != torch.float64 or hyper.numel() < 3 or state.numel() < 1:
+        raise ValueError("sgd_step: state / hyper must be the optimizer's float64 device arrays")
+    if max_wg is None or max_wg < 0:
+        raise ValueError("sgd_step: max_wg must be >= 0")
+    n = p.numel()
+    if g.numel() != n or (buf is not None and buf.numel() != n) or (p_bf16 is not None and p_bf16.numel() != n):
+        raise ValueError("sgd_step: p, g, buf and p_bf16 must have one length")
+    td, nt, wt = None, 0, None
+    if transposed is not None:
+        td, host, wt = transposed
+        nt = len(host)
+        for rows, cols, off, lds, doff, ldd in host:
+            if lds % 4 or cols % 4 or off % 4 or tbase % 4 or off < tbase or off + rows * lds > tbase + (n // 4) * 4 \
+                    or doff < 0 or doff + (cols - 1) * ldd + rows > wt.numel() or rows * lds >= 2 ** 31 \
+                    or cols > lds or rows <= 0 or cols <= 0 or ldd < rows:
+                raise ValueError("sgd_step: transposed matrix outside the buffers or misaligned")
+        if p_bf16 is None:
+            raise ValueError("sgd_step: transposed copies need the bf16 output")
+    call("rs_sgd_step", n, ptr(p), ptr(g), ptr(buf), ptr(p_bf16), ptr(state), ptr(hyper), int(zero_grad),
+         int(prepare), ptr(grad_divisor), ptr(seed_base), ptr(td), nt, int(tbase), ptr(wt), ptr(loss_sum),
+         ptr(loss_out), int(max_wg), stream())
+
+
 L2_CHUNK = 16384
 
 

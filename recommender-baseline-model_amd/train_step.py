@@ -21,6 +21,7 @@ compute and optimizer graphs around the eager RCCL call under DP) and
 dropout step-seed lives in device memory and is advanced inside the graph.
 """
 import gc
+import math
 import os
 import warnings
 
@@ -174,8 +175,54 @@ class FusedAdam:
             ops.seed_advance(seed_base)
 
 
+class FusedSGD:
+    """Device-side torch.optim.SGD(params, lr, momentum=, weight_decay=) over a FlatParams buffer (rs_sgd_step): the
+    reference's other optimizer (BS/trainers/base.py:229-233; dampening 0, nesterov False).  hyper[0] is the rate, so
+    FusedStepLR drives it through set_lr as it drives FusedAdam; state[0] is the device step count."""
+
+    MAX_WG = 8192      # rs_adam_step's grid bound
+
+    def __init__(self, flat, lr, momentum=0.0, weight_decay=0.0):
+        dev = flat.device
+        self.flat = flat
+        self.momentum = float(momentum)
+        self.weight_decay = float(weight_decay)
+        # the momentum buffer, zero-initialised: torch's first-step rule (buf = grad.clone()) falls out of the update
+        self.buf = torch.zeros(flat.numel, dtype=torch.float32, device=dev) if self.momentum != 0 else None
+        self.state = torch.zeros(8, dtype=torch.float64, device=dev)
+        self.hyper = torch.tensor([lr, self.momentum, self.weight_decay], dtype=torch.float64, device=dev)
+        self.marks = None      # no row-marked sweeps under SGD
+
+    def set_lr(self, lr):
+        """StepLR hook (BS/trainers/base.py:40,87): lives on the device, so graph replays see it."""
+        self.hyper[0] = lr
+
+    def step(self, grad_divisor=None, seed_base=None, ranges=None, transposed=None, loss=None, keep=None,
+             sparse=None):
+        """One SGD update, FusedAdam.step's range semantics: ranges = [(lo, hi)] flat slices (default all); the first
+        range's launch also advances the step count and the seed and forms loss = (sum, out) (prepare=1) and carries
+        the transposed copies; keep = (lo, hi): a slice updated by its own launch that leaves its gradient in
+        place.  Every other range's gradient is cleared."""
+        if sparse:
+            raise ValueError("FusedSGD has no sparse (touched-rows-only) rule: the lazy rule is Adam's")
+        f = self.flat
+        segs = [(lo, hi, True) for lo, hi in (ranges or [(0, f.numel)])]
+        if keep is not None and ranges is None:
+            klo, khi = keep
+            assert 0 < klo < khi <= f.numel and klo % 4 == 0 and khi % 4 == 0, keep
+            segs = [(0, klo, True), (klo, khi, False)] + ([(khi, f.numel, True)] if khi < f.numel else [])
+        for k, (lo, hi, zg) in enumerate(segs):
+            first = k == 0
+            ops.sgd_step(f.data[lo:hi], f.grad[lo:hi], self.buf[lo:hi] if self.buf is not None else None,
+                         f.bf16[lo:hi] if f.bf16 is not None else None, self.state, self.hyper, zero_grad=zg,
+                         prepare=first, grad_divisor=grad_divisor, seed_base=seed_base if first else None,
+                         transposed=transposed if first else None, tbase=lo,
+                         loss_sum=loss[0] if loss and first else None, loss_out=loss[1] if loss and first else None,
+                         max_wg=self.MAX_WG)
+
+
 class FusedStepLR:
-    """``torch.optim.lr_scheduler.StepLR(optimizer, step_size, gamma)`` for a FusedAdam (BS/trainers/base.py:40, stepped
+    """``torch.optim.lr_scheduler.StepLR(optimizer, step_size, gamma)`` for a FusedAdam or FusedSGD (BS/trainers/base.py:40, stepped
     once per epoch at :87): every ``step_size``-th ``step()`` multiplies the learning rate by ``gamma`` -- chained in
     Python floats exactly as torch's StepLR forms it -- and writes it into the optimizer's device hyperparameters, so
     captured step graphs replayed afterwards use it without re-capture."""
@@ -205,8 +252,18 @@ class FusedStepLR:
 class FusedTrainStep:
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
                  bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None,
-                 logq=None, table_optim="dense"):
+                 logq=None, table_optim="dense", optimizer="adam", momentum=0.0):
         """model: rbm_amd SASModel or BERTModel on a CUDA device.
+        optimizer: "adam" (default: torch.optim.Adam, BS/trainers/base.py:225-228) or "sgd" (torch.optim.SGD(params,
+        lr, weight_decay=weight_decay, momentum=momentum), BS/trainers/base.py:229-233), case-insensitive as the
+        reference lowercases args.optimizer.  "sgd" runs every loss of the step on one device and plain data parallel
+        (the all-reduce of the flat gradient, bucketed or overlapped, BERT's sparse_rows exchange); the whole update
+        runs at the end of the step (no early head / token update, no row marks).  Refused with ValueError:
+        table_optim="sparse" (the lazy rule is Adam's), shard_rows="on" ("auto" resolves to off), vocab_shard, and a
+        momentum that is None, negative or not finite.  Under "adam" momentum is not read, as in the reference: None
+        (its default) and 0 pass, a non-zero number is a ValueError.  Checkpoints are in torch.optim.SGD's state_dict
+        format (momentum_buffer per parameter); a loaded momentum that would add or drop the buffer under captured
+        graphs is refused.
         table_optim: "dense" (default: the reference's torch.optim.Adam on every parameter, bit for bit) or "sparse":
         the embedding / output tables of a sampled loss take the lazy rule (FusedAdam.step(sparse=...): rows without
         a gradient this step are left alone, as torch's SparseAdam / TensorFlow's LazyAdam do), so the optimizer's
@@ -246,6 +303,30 @@ class FusedTrainStep:
         them (needs l2_emb == 0: the regulariser reads every master row)."""
         self.model = model
         self.kind = model.code()
+        # the optimizer switch: every refusal before the first launch and before the device is touched
+        if not isinstance(optimizer, str) or optimizer.lower() not in ("adam", "sgd"):
+            raise ValueError(f"optimizer must be 'adam' or 'sgd' (the reference's args.optimizer), got {optimizer!r}")
+        self.optimizer = optimizer.lower()
+        if self.optimizer == "adam":
+            # the reference reads args.momentum in its SGD branch only, and its default is None: None (and 0) pass
+            if momentum is not None and (isinstance(momentum, bool) or momentum != 0):
+                raise ValueError(f"momentum={momentum!r} needs optimizer='sgd' (Adam takes none)")
+            momentum = 0.0
+        elif momentum is None or isinstance(momentum, bool) or not isinstance(momentum, (int, float)) \
+                or not math.isfinite(momentum) or momentum < 0:
+            raise ValueError(f"optimizer='sgd': momentum must be a finite number >= 0, got {momentum!r} (the "
+                             "reference's own default, momentum=None, makes torch.optim.SGD raise too: pass a number)")
+        self.momentum = float(momentum)
+        if self.optimizer == "sgd":
+            if table_optim == "sparse":
+                raise ValueError("table_optim='sparse' needs optimizer='adam': the lazy rule is Adam's")
+            if shard_rows == "on":
+                raise ValueError("shard_rows='on' needs optimizer='adam': the sharded item-table optimizer is not "
+                                 "covered under SGD")
+            if vocab_shard:
+                raise ValueError("vocab_shard needs optimizer='adam': the vocabulary-sharded head is not covered "
+                                 "under SGD")
+            shard_rows = "off"
         if loss is None:
             loss = getattr(model.sas, "sas_loss", "bce") if self.kind == "sas" else None
             if self.kind == "bert" and getattr(model.bert, "bert_loss", "ce") == "sampled_ce":
@@ -298,7 +379,10 @@ class FusedTrainStep:
         if hasattr(self.engine, "adam_transposes"):
             self.engine.adam_transposes = True  # SAS: the optimizer kernel also writes the transposed block weights
         self.flat.grad.zero_()                 # then kept zero by the optimizer (zero_grad)
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
+        if self.optimizer == "sgd":
+            self.opt = FusedSGD(self.flat, lr=lr, momentum=self.momentum, weight_decay=weight_decay)
+        else:
+            self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
         self.pg = process_group
         self.dp = dpx.world() > 1 if dp is None else bool(dp)
         self.bucket_numel = bucket_numel
@@ -378,7 +462,9 @@ class FusedTrainStep:
         self._early_forked = False     # this step forked an early update that _update has yet to join
         # Not with the sampled-softmax head: it accumulates into a zeroed out.weight / out.bias gradient (no
         # overwritten range), and its index launches finish on the side stream only at the end of the backward.
+        # Nor under SGD: its whole update runs at the end of the step.
         self._early_ok = (self.kind == "bert" and self.loss != "sampled_ce" and not self.dp and self.vshard is None
+                          and self.optimizer == "adam"
                           and not self.l2
                           and os.environ.get("RS_EARLY_HEAD_ADAM", "1") != "0"
                           and hasattr(self.engine, "overwritten_grads"))
@@ -403,7 +489,8 @@ class FusedTrainStep:
         tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce")
         # A sparse table takes no marks either: its untouched rows are not swept at all.
         sparse = table_optim == "sparse"
-        if tied_head or sparse:
+        sgd = self.optimizer == "sgd"       # the marked sweeps are Adam's: marks stay off under SGD
+        if tied_head or sparse or sgd:
             self.engine.row_marks = None
         # sparse tables: [(key positions in the batch, [(flat offset, rows, d)])] -- one union list per entry, shared
         # by its tables (out.weight and out.bias); the lists and their workspaces are allocated by the first step
@@ -422,7 +509,7 @@ class FusedTrainStep:
                 self._sparse_tables = [((0,), [tab("bert.embedding.token.weight")]),
                                        ((1, 2), [tab("out.weight"), tab("out.bias")])]
             self._rows_side = SideBranch(dev, avoid=taken + [self._capture_side.stream])
-        if (not self.dp and not self.l2 and not tied_head and not sparse
+        if (not self.dp and not self.l2 and not tied_head and not sparse and not sgd
                 and os.environ.get("RS_ROW_MARKS", "1") != "0"
                 and hasattr(self.engine, "enable_row_marks")):
             r = self.engine.enable_row_marks(self.ROW_MARKS_MIN)
@@ -780,6 +867,8 @@ class FusedTrainStep:
         the same parameters; per-parameter 'step', 'exp_avg', 'exp_avg_sq'), so the reference trainer can
         resume from it (BS/trainers/base.py:255-259, 'optimizer_state_dict').  With the sharded item table and stale
         rows (after a step) this is COLLECTIVE: call it on every rank, not from rank 0 alone."""
+        if self.optimizer == "sgd":
+            return self._sgd_state_dict()
         if self.rshard is not None and self.flat.stale:
             self.gather_shards()
         torch.cuda.synchronize()
@@ -796,8 +885,14 @@ class FusedTrainStep:
         return sd
 
     def load_optimizer_state_dict(self, sd):
-        """Resume from a torch.optim.Adam state_dict (e.g. a reference checkpoint's 'optimizer_state_dict')."""
+        """Resume from a torch.optim.Adam state_dict (e.g. a reference checkpoint's 'optimizer_state_dict'); under
+        optimizer="sgd", from a torch.optim.SGD one.  The other optimizer's format is a ValueError."""
         g = sd["param_groups"][0]
+        if self.optimizer == "sgd":
+            return self._load_sgd_state_dict(sd)
+        if "betas" not in g:
+            raise ValueError("optimizer='adam' cannot load this optimizer state: its param_groups have no 'betas' (a "
+                             "torch.optim.SGD checkpoint loads into a step built with optimizer='sgd')")
         if self.table_optim == "sparse" and g["weight_decay"] != 0:
             raise ValueError("table_optim='sparse' needs weight_decay == 0 (the loaded optimizer state has "
                              f"{g['weight_decay']})")
@@ -820,6 +915,67 @@ class FusedTrainStep:
             raise ValueError("per-parameter Adam step counts differ; the fused optimizer keeps one")
         self.opt.state.zero_()
         self.opt.state[0] = steps.pop() if steps else 0.0
+
+    # torch.optim.SGD's state_dict carries no step count: the device count (kernel stamps, resumed runs) travels in
+    # this extra param_groups key, which torch.optim.SGD.load_state_dict keeps and never reads
+    SGD_STEP_KEY = "fused_step"
+
+    def _sgd_state_dict(self):
+        """torch.optim.SGD's state_dict() layout: param_groups from a real SGD over the same parameters (torch's own
+        keys) plus SGD_STEP_KEY; state[i] = {'momentum_buffer'} per parameter once a step has run with a non-zero
+        momentum, else empty."""
+        torch.cuda.synchronize()
+        lr, mom, wd = self.opt.hyper.cpu().tolist()
+        sd = torch.optim.SGD(self.model.parameters(), lr=lr, momentum=mom, weight_decay=wd).state_dict()
+        step = float(self.opt.state[0].item())
+        sd["param_groups"][0][self.SGD_STEP_KEY] = step
+        if step > 0 and self.opt.buf is not None:
+            for i, (p, off) in enumerate(self._param_slices()):
+                n = p.numel()
+                sd["state"][i] = {"momentum_buffer": self.opt.buf[off:off + n].view(p.shape).detach().cpu().clone()}
+        return sd
+
+    def _load_sgd_state_dict(self, sd):
+        g = sd["param_groups"][0]
+        if "betas" in g or "momentum" not in g:
+            raise ValueError("optimizer='sgd' cannot load this optimizer state: its param_groups are not "
+                             "torch.optim.SGD's (an Adam checkpoint loads into a step built with optimizer='adam')")
+        if g.get("dampening", 0) != 0:
+            raise ValueError(f"dampening must be 0 (the loaded optimizer state has {g['dampening']}): the fused SGD "
+                             "has none")
+        if g.get("nesterov", False):
+            raise ValueError("nesterov must be False (the loaded optimizer state has nesterov=True): the fused SGD "
+                             "has none")
+        mom = float(g["momentum"])
+        if not math.isfinite(mom) or mom < 0:
+            raise ValueError(f"momentum must be a finite number >= 0 (the loaded optimizer state has {mom})")
+        opt = self.opt
+        if (mom != 0) != (opt.buf is not None) and self.graphs is not None:
+            # a captured graph holds the buffer's pointer and the kernel chosen for its presence: a new or a dropped
+            # buffer would leave the graph on the old one
+            raise ValueError(f"the loaded optimizer state has momentum={mom}, the captured step graphs were built "
+                             f"with momentum={self.momentum}: load it before capture(), or build the step with "
+                             "that momentum")
+        if mom != 0 and opt.buf is None:
+            opt.buf = torch.zeros(self.flat.numel, dtype=torch.float32, device=self.flat.device)
+        elif mom == 0:
+            opt.buf = None
+        opt.momentum = self.momentum = mom
+        opt.weight_decay = float(g["weight_decay"])
+        opt.hyper.copy_(torch.tensor([g["lr"], mom, g["weight_decay"]], dtype=torch.float64))
+        seen = 0
+        if opt.buf is not None:
+            opt.buf.zero_()
+            for i, (p, off) in enumerate(self._param_slices()):
+                st = sd["state"].get(i)
+                b = st.get("momentum_buffer") if st else None
+                if b is None:       # torch: no buffer yet -> its first step clones the gradient, as a zero one does
+                    continue
+                opt.buf[off:off + p.numel()].copy_(b.reshape(-1))
+                seen += 1
+        opt.state.zero_()
+        # a checkpoint torch.optim.SGD wrote has no count: 1 when it holds buffers (some step ran), else 0
+        opt.state[0] = float(g.get(self.SGD_STEP_KEY, 1.0 if seen else 0.0))
 
     def gather_vocab_shards(self):
         """Vocabulary-sharded step: make this rank's out.weight / out.bias (and their Adam moments) hold every
