@@ -612,6 +612,30 @@ int rs_sas_block_in_out_bwd(int64_t d, const rs_sas_in_bwd_args* in_bwd, const r
 int rs_sas_block_out_head_bwd(int64_t d, const rs_sas_out_args* out, const rs_sas_out_bwd_args* out_bwd,
                               void* stream);
 
+/* The first block's embed-form input side and its attention forward (one head, causal) in ONE launch
+ * (block_in_attn.hip): rs_sas_block_in(in, embed form) followed by rs_attn_fwd(q = in.q, k / v = the halves of in.kv,
+ * mask_kind 0, seed = salt, seed_base = in.e.seed_base) on B sequences of in.e.T rows, bit for bit, for every tensor
+ * either writes.  The grid is the attention forward's; each workgroup forms its sequence's K/V image in LDS with the
+ * row chain's stages, so nothing is reloaded across a launch boundary. */
+typedef struct rs_sas_in_attn_args {
+  rs_sas_in_args in;           /* the embed form (in.e.item_emb required); M = B * in.e.T; x / ldx set by the entry */
+  int64_t B;                   /* sequences */
+  rs_bf16* o;                  /* [M][d] out: the attention output, 16-byte aligned */
+  float* lse;                  /* [M] out: row logsumexp */
+  float scale;                 /* score scale (1 / sqrt(d)) */
+  float drop_p;                /* attention dropout */
+  uint64_t salt;               /* its site salt (rs_attn_fwd's seed) */
+  int64_t ncount;              /* slots of in.e.count_parts, >= nsplit * B: EVERY slot is written (workgroup counts,
+                                  then zeros), so rs_sas_head_args.count_parts may be summed over all of them */
+} rs_sas_in_attn_args;
+/* Host-only: the workgroups per sequence of rs_sas_block_in_attn for (d, B, T), or 0 where it does not cover the
+ * shape and returns RS_ERR_UNSUPPORTED (d not in {64, 128}; T or the dropout index outside the LDS attention's range;
+ * more than 8 query tiles per workgroup; the images and one weight slot beyond the 160 KB of LDS). */
+int rs_sas_block_in_attn_nsplit(int64_t d, int64_t B, int64_t T);
+/* RS_ERR_ARG (nothing launched) for a NULL or misaligned tensor, M != B * in.e.T, count_ids without count_parts (or
+ * the reverse) or ncount < nsplit * B. */
+int rs_sas_block_in_attn(int64_t d, const rs_sas_in_attn_args* args, void* stream);
+
 /* Union-of-touched-rows exchange of an embedding-table gradient (sparse_rows.hip; data parallel,
  * replaces the dense all-reduce of the token / item table gradient -- the reference has no
  * multi-GPU path, BS/trainers/base.py:32-34).  rs_touched_rows: flags[v] = (v occurs in ids[0..n)),
@@ -1013,7 +1037,8 @@ enum {
   RS_SIZEOF_SAS_HEAD_ARGS = 5,
   RS_SIZEOF_SAS_OUT_ARGS = 6,
   RS_SIZEOF_SAS_OUT_BWD_ARGS = 7,
-  RS_SIZEOF_SAS_IN_BWD_ARGS = 8
+  RS_SIZEOF_SAS_IN_BWD_ARGS = 8,
+  RS_SIZEOF_SAS_IN_ATTN_ARGS = 9
 };
 int64_t rs_abi_sizeof(int which);
 

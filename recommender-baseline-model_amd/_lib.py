@@ -86,10 +86,17 @@ class SasInBwdArgs(C.Structure):
                 ("ln_w", vp), ("WinT", vp), ("ldwt", i64), ("dx", vp), ("part", vp)]
 
 
+class SasInAttnArgs(C.Structure):
+    """Mirror of ``rs_sas_in_attn_args``."""
+    _fields_ = [("in", SasInArgs), ("B", i64), ("o", vp), ("lse", vp), ("scale", f32), ("drop_p", f32), ("salt", u64),
+                ("ncount", i64)]
+
+
 # header struct name -> mirror, in the order of rs_abi_sizeof's indices (RS_SIZEOF_*)
 STRUCTS = {"rs_epilogue": Epilogue, "rs_wgrad_problem": WgradProblem, "rs_reduce_segment": ReduceSegment,
            "rs_sas_embed_args": SasEmbedArgs, "rs_sas_in_args": SasInArgs, "rs_sas_head_args": SasHeadArgs,
-           "rs_sas_out_args": SasOutArgs, "rs_sas_out_bwd_args": SasOutBwdArgs, "rs_sas_in_bwd_args": SasInBwdArgs}
+           "rs_sas_out_args": SasOutArgs, "rs_sas_out_bwd_args": SasOutBwdArgs, "rs_sas_in_bwd_args": SasInBwdArgs,
+           "rs_sas_in_attn_args": SasInAttnArgs}
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_BWD, ACT_GELU_BWD = 0, 1, 2, 3, 4
 
@@ -163,6 +170,8 @@ SIGNATURES = {
     "rs_sas_block_out_bwd": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, u64, u64,
                              vp, vp],
     "rs_sas_block_in_bwd": [i64, C.POINTER(SasInBwdArgs), vp],
+    "rs_sas_block_in_attn": [i64, C.POINTER(SasInAttnArgs), vp],
+    "rs_sas_block_in_attn_nsplit": [i64, i64, i64],
     "rs_sas_block_out_in": [i64, C.POINTER(SasOutArgs), C.POINTER(SasInArgs), vp],
     "rs_sas_block_in_out_bwd": [i64, C.POINTER(SasInBwdArgs), C.POINTER(SasOutBwdArgs), vp],
     "rs_sas_block_out_head_bwd": [i64, C.POINTER(SasOutArgs), C.POINTER(SasOutBwdArgs), vp],

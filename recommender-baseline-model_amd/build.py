@@ -10,6 +10,7 @@ rebuilt only when it (or a header) is newer than its object.
 import concurrent.futures as cf
 import glob
 import os
+import re
 import subprocess
 import sys
 
@@ -24,7 +25,7 @@ ARCH = os.environ.get("RS_OFFLOAD_ARCH", "gfx950")
 # objects, and a unit inserted in the middle moves every later one: with sas_ce.hip at its alphabetical place the
 # cfg2 BCE step (which launches nothing of it) measured 0.2763 ms against 0.2748 before the unit existed and 0.2737
 # with it linked last (means of six interleaved bench.py runs each).  New units go here.
-LINK_LAST = ("sas_ce.hip", "sas_sce.hip", "adam_rows.hip", "sgd.hip")
+LINK_LAST = ("sas_ce.hip", "sas_sce.hip", "adam_rows.hip", "sgd.hip", "block_in_attn.hip")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -44,10 +45,19 @@ def _included_mtime():
     return max((os.path.getmtime(p) for p in inc), default=0.0)
 
 
+def _hip_includes_mtime(src):
+    """a unit may also include another compiled unit for its device code (block_in_attn.hip: rowchain.hip and
+    attention_lds.hip, whose entry points are guarded out there)"""
+    with open(src) as fh:
+        inc = re.findall(r'^#include "(\w+\.hip)"', fh.read(), flags=re.M)
+    return max((os.path.getmtime(os.path.join(CSRC, i)) for i in inc), default=0.0)
+
+
 def _compile(src, force):
     obj = os.path.join(OBJ, os.path.basename(src) + ".o")
     if not force and os.path.exists(obj):
-        if os.path.getmtime(obj) >= max(os.path.getmtime(src), _headers_mtime(), _included_mtime()):
+        if os.path.getmtime(obj) >= max(os.path.getmtime(src), _headers_mtime(), _included_mtime(),
+                                       _hip_includes_mtime(src)):
             return obj, False
     cmd = [HIPCC, *FLAGS, "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -309,6 +309,109 @@ __device__ __forceinline__ int last_tile_of_split(int nq, int split, int nsplit)
 }
 
 // ------------------------------------------------------------------ forward
+// one 16-query tile of the forward: scores against the key image, softmax, dropout, O = P V, the lse and o stores.
+// qf: the tile's q rows as B fragments (lane (g, cl): row 16 qt + cl, columns 32 kc + 8g .. + 7; zero past T).
+// (attn_fwd_lds_kernel's loop body; block_in_attn.hip runs it on images and q fragments it formed itself)
+template <int DH>
+__device__ __forceinline__ void attn_fwd_tile(const AttnLdsArgs& a, const bf16* Ks, const bf16* Vs, const float* km,
+                                              const bf16x8 (&qf)[DH / 32], int qt, int64_t bh, int64_t b, int64_t h,
+                                              int T, int nq, uint64_t seed, int lane) {
+  constexpr int LD = Img<DH>::LD, KC = DH / 32, DT = DH / 16, NKT = 16;
+  const int g = lane >> 4, cl = lane & 15;
+  const int q0 = qt * 16;
+  const int64_t qrow = q0 + cl;  // this lane's query
+  const int nkt = a.mask_kind == 0 ? qt + 1 : nq;
+  const float sl2 = a.scale * LOG2E;
+  const int qi = q0 + cl;
+  f32x4 s[NKT];
+  float mx = NEG_INF;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (kt < nkt) {
+#pragma unroll
+      for (int kc = 0; kc < KC; ++kc) s[kt] = mfma16(row_frag(Ks, LD, kt * 16 + cl, kc * 32 + 8 * g), qf[kc], s[kt]);
+      // per-element masking only where a tile can hold masked scores (wave-uniform test); selects, not
+      // exec-mask branches (the key-padding flags are one vector load, 0 when causal)
+      const bool need = a.mask_kind != 0 || kt == qt || kt * 16 + 16 > T;
+      const int kb = kt * 16 + 4 * g;
+      if (need) {
+        const f32x4 kmv = *reinterpret_cast<const f32x4*>(km + kb);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int k = kb + r;
+          const bool dead = (k >= T) | ((a.mask_kind == 0) & (k > qi));
+          const float x = s[kt][r] * sl2;
+          s[kt][r] = dead ? NEG_INF : (kmv[r] != 0.f ? MASK2 : x);
+          mx = fmaxf(mx, s[kt][r]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s[kt][r] *= sl2;
+          mx = fmaxf(mx, s[kt][r]);
+        }
+      }
+    }
+  }
+  mx = max_xor32(max_xor16(mx));
+  float sm = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    if (kt < nkt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = ex2(s[kt][r] - mx);
+        s[kt][r] = e;
+        sm += e;
+      }
+    }
+  }
+  sm = add_xor32(add_xor16(sm));
+  const float inv = 1.f / sm;
+  if (g == 0 && qrow < a.T) a.lse[bh * a.T + qrow] = (mx + __builtin_amdgcn_logf(sm)) * LN2;
+  // P^T (+ dropout: one hash per pair of adjacent keys), packed pairwise as the B operand of O^T = V^T P^T
+  const uint32_t s32 = seed32(seed);
+  const uint32_t rowidx = (uint32_t)(((int)bh * T + qi) * (T + (T & 1)));   // mask row pitch: even
+  f32x4 o[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < NKT / 2; ++c) {
+    if (2 * c < nkt) {
+      f32x4 pp[2] = {s[2 * c], s[2 * c + 1]};
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int t = 2 * c + hf;
+        const float sc = t < nkt ? inv : 0.f;
+        if (a.drop_p > 0.f) {
+          float m[4];
+          const uint32_t base = rowidx + (uint32_t)(t * 16 + 4 * g);
+          drop_mul2(a.drop_p, s32, base, m[0], m[1]);
+          drop_mul2(a.drop_p, s32, base + 2, m[2], m[3]);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pp[hf][r] *= sc * m[r];
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pp[hf][r] *= sc;
+        }
+      }
+      const bf16x8 pb = pack8(pp[0], pp[1]);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(tr_frag(Vs, LD, 32 * c, 16 * dt, lane), pb, o[dt]);
+    }
+  }
+  if (qrow < a.T) {
+    bf16* O = a.out + (b * a.T + qrow) * a.ldout + h * DH;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      bf4 w;
+      w[0] = (bf16)o[dt][0]; w[1] = (bf16)o[dt][1]; w[2] = (bf16)o[dt][2]; w[3] = (bf16)o[dt][3];
+      *reinterpret_cast<bf4*>(O + 16 * dt + 4 * g) = w;
+    }
+  }
+}
+
 template <int DH>
 __global__ __launch_bounds__(NT) void attn_fwd_lds_kernel(AttnLdsArgs a) {
   constexpr int LD = Img<DH>::LD, KC = DH / 32, DT = DH / 16, NKT = 16;
@@ -350,106 +453,19 @@ __global__ __launch_bounds__(NT) void attn_fwd_lds_kernel(AttnLdsArgs a) {
   if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
 
   for (int qt = split + wave * a.nsplit; qt < nq; qt += NW * a.nsplit) {
-    const int q0 = qt * 16;
-    const int64_t qrow = q0 + cl;  // this lane's query
     if (qt != split + wave * a.nsplit) {
+      const int64_t qrow = qt * 16 + cl;  // this lane's query
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) qf[kc] = gload8(Qg, a.ldq, qrow, a.T, kc * 32 + 8 * g);
     }
-    const int nkt = a.mask_kind == 0 ? qt + 1 : nq;
-    const float sl2 = a.scale * LOG2E;
-    const int qi = q0 + cl;
-    f32x4 s[NKT];
-    float mx = NEG_INF;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (kt < nkt) {
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) s[kt] = mfma16(row_frag(Ks, LD, kt * 16 + cl, kc * 32 + 8 * g), qf[kc], s[kt]);
-        // per-element masking only where a tile can hold masked scores (wave-uniform test); selects, not
-        // exec-mask branches (the key-padding flags are one vector load, 0 when causal)
-        const bool need = a.mask_kind != 0 || kt == qt || kt * 16 + 16 > T;
-        const int kb = kt * 16 + 4 * g;
-        if (need) {
-          const f32x4 kmv = *reinterpret_cast<const f32x4*>(km + kb);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int k = kb + r;
-            const bool dead = (k >= T) | ((a.mask_kind == 0) & (k > qi));
-            const float x = s[kt][r] * sl2;
-            s[kt][r] = dead ? NEG_INF : (kmv[r] != 0.f ? MASK2 : x);
-            mx = fmaxf(mx, s[kt][r]);
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            s[kt][r] *= sl2;
-            mx = fmaxf(mx, s[kt][r]);
-          }
-        }
-      }
-    }
-    mx = max_xor32(max_xor16(mx));
-    float sm = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      if (kt < nkt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = ex2(s[kt][r] - mx);
-          s[kt][r] = e;
-          sm += e;
-        }
-      }
-    }
-    sm = add_xor32(add_xor16(sm));
-    const float inv = 1.f / sm;
-    if (g == 0 && qrow < a.T) a.lse[bh * a.T + qrow] = (mx + __builtin_amdgcn_logf(sm)) * LN2;
-    // P^T (+ dropout: one hash per pair of adjacent keys), packed pairwise as the B operand of O^T = V^T P^T
-    const uint32_t s32 = seed32(seed);
-    const uint32_t rowidx = (uint32_t)(((int)bh * T + qi) * (T + (T & 1)));   // mask row pitch: even
-    f32x4 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < NKT / 2; ++c) {
-      if (2 * c < nkt) {
-        f32x4 pp[2] = {s[2 * c], s[2 * c + 1]};
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          const int t = 2 * c + hf;
-          const float sc = t < nkt ? inv : 0.f;
-          if (a.drop_p > 0.f) {
-            float m[4];
-            const uint32_t base = rowidx + (uint32_t)(t * 16 + 4 * g);
-            drop_mul2(a.drop_p, s32, base, m[0], m[1]);
-            drop_mul2(a.drop_p, s32, base + 2, m[2], m[3]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pp[hf][r] *= sc * m[r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pp[hf][r] *= sc;
-          }
-        }
-        const bf16x8 pb = pack8(pp[0], pp[1]);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(tr_frag(Vs, LD, 32 * c, 16 * dt, lane), pb, o[dt]);
-      }
-    }
-    if (qrow < a.T) {
-      bf16* O = a.out + (b * a.T + qrow) * a.ldout + h * DH;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        bf4 w;
-        w[0] = (bf16)o[dt][0]; w[1] = (bf16)o[dt][1]; w[2] = (bf16)o[dt][2]; w[3] = (bf16)o[dt][3];
-        *reinterpret_cast<bf4*>(O + 16 * dt + 4 * g) = w;
-      }
-    }
+    attn_fwd_tile<DH>(a, Ks, Vs, km, qf, qt, bh, b, h, T, nq, seed, lane);
   }
   APROF(2);
 }
 
+// block_in_attn.hip includes this file for the device code above (ATTN_LDS_DEVICE_ONLY): the backward, the launchers
+// and the host functions below belong to this translation unit alone
+#ifndef ATTN_LDS_DEVICE_ONLY
 // ------------------------------------------------------------------ backward: delta + dQ
 template <int DH>
 __device__ __forceinline__ void attn_bwd_dq_body(const AttnLdsArgs& a, int64_t lin) {
@@ -969,6 +985,8 @@ bool attn_lds_supported(int64_t T, int64_t Dh) {
 
 // the forward's workgroups per sequence-head (the launcher and rs_attn_lds_regime)
 static int fwd_split(const AttnLdsArgs& a) { return pick_split(a.B * a.H, (int)cdiv(a.T, 16)); }
+// the same, for block_in_attn.hip's launcher (its grid is the forward's)
+int attn_lds_fwd_nsplit(int64_t BH, int64_t T) { return pick_split(BH, (int)cdiv(T, 16)); }
 
 template <int DH>
 static hipError_t fwd_t(AttnLdsArgs& a, hipStream_t s) {
@@ -1155,3 +1173,4 @@ hipError_t attn_lds_bwd(int64_t B, int64_t T, int64_t H, int64_t Dh, const void*
   if (Dh == 64) return bwd_t<64>(a, s);
   return bwd_t<32>(a, s);
 }
+#endif  // ATTN_LDS_DEVICE_ONLY

@@ -598,6 +598,7 @@ int64_t rs_abi_sizeof(int which) {
     case RS_SIZEOF_SAS_OUT_ARGS: return sizeof(rs_sas_out_args);
     case RS_SIZEOF_SAS_OUT_BWD_ARGS: return sizeof(rs_sas_out_bwd_args);
     case RS_SIZEOF_SAS_IN_BWD_ARGS: return sizeof(rs_sas_in_bwd_args);
+    case RS_SIZEOF_SAS_IN_ATTN_ARGS: return sizeof(rs_sas_in_attn_args);
     default: return -1;
   }
 }

@@ -1,7 +1,8 @@
 // Wave-resident row chains for the SASRec sublayers (bf16, gfx950): the kernels behind
 // rs_sas_block_in / rs_sas_block_out / rs_sas_block_out_bwd / rs_sas_block_in_bwd and the two-chain entries
 // rs_sas_block_out_in / rs_sas_block_in_out_bwd / rs_sas_block_out_head_bwd.  Their arguments are the public structs
-// of recsys_hip.h, taken by the kernels as they are.
+// of recsys_hip.h, taken by the kernels as they are.  block_in_attn.hip (rs_sas_block_in_attn) includes this file for
+// the device code (RC_DEVICE_ONLY) and runs the input-side stages inside the attention forward's grid.
 //
 // Everything in a SAS block except the attention core is row-local (BS/models/sas_model/sas.py:73-76 before the
 // core: Q = LN1(x), q = Q Wq^T + bq, kv = x Wkv^T + bkv; sas.py:75-84 after it: x1 = Q + O Wo^T + bo, z = LN2(x1),
@@ -150,6 +151,34 @@ __device__ __forceinline__ void mm(const bf16* wl, const Raw<D>& b, Act<D>& acc,
 #pragma unroll
     for (int s = 0; s < S; ++s)
       acc.v[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[j & 1][s], b.v[s], acc.v[j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// mm for the two token tiles of one wave (block_in_attn.hip): every weight fragment is read from LDS once and multiplies
+// both B operands; each accumulator sees the MFMA sequence mm gives it
+template <int D>
+__device__ __forceinline__ void mm2(const bf16* wl, const Raw<D>& b0, const Raw<D>& b1, Act<D>& acc0, Act<D>& acc1,
+                                    int lane) {
+  constexpr int J = Lay<D>::J, S = Lay<D>::S;
+  const int g = lane >> 4, cl = lane & 15;
+  auto frag = [&](int j, int s) {
+    const int n = 16 * j + cl;
+    return *reinterpret_cast<const bf16x8*>(wl + n * D + 8 * ((4 * s + g) ^ swz<D>(n)));
+  };
+  bf16x8 f[2][S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) f[0][s] = frag(0, s);
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    if (j + 1 < J) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) f[(j + 1) & 1][s] = frag(j + 1, s);
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      acc0.v[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[j & 1][s], b0.v[s], acc0.v[j], 0, 0, 0);
+      acc1.v[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[j & 1][s], b1.v[s], acc1.v[j], 0, 0, 0);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -374,9 +403,10 @@ __device__ __forceinline__ Tile tile_of(int64_t t, int64_t M, int cl) {
 // ------------------------------------------------------------------ chain stages (one 16-token tile per wave)
 // Forward, block input side (sas.py:73-76): Q = LN1(x) [saved], q = Q Wq^T + bq.  Weights/vectors: Wq at wq;
 // lv: ln1_w, ln1_b, bq, bk, bv (5 x D).  Returns nothing; k/v follow in fwd_in_kv.
+// (fwd_in_q_x also hands back the rounded q: block_in_attn.hip's attention reads it from registers)
 template <int D>
-__device__ __forceinline__ void fwd_in_q(const Raw<D>& xr, const Tile& T, const bf16* wq, const float* lv, float eps,
-                                         bf16* Q, float* mean, float* rstd, bf16* q, int lane) {
+__device__ __forceinline__ void fwd_in_q_x(const Raw<D>& xr, const Tile& T, const bf16* wq, const float* lv, float eps,
+                                           bf16* Q, float* mean, float* rstd, bf16* q, int lane, Raw<D>& r) {
   const int g = lane >> 4;
   Act<D> y;
   to_act<D>(y, xr);
@@ -394,25 +424,57 @@ __device__ __forceinline__ void fwd_in_q(const Raw<D>& xr, const Tile& T, const 
   mm<D>(wq, Qr, acc, lane);
 #pragma unroll
   for (int j = 0; j < Lay<D>::J; ++j) acc.v[j] += vec4<D>(lv + 2 * D, j, g);
-  Raw<D> r;
   round_act<D>(acc, r);
   store_raw<D>(q, D, T.m, T.ok, r, g);
+}
+template <int D>
+__device__ __forceinline__ void fwd_in_q(const Raw<D>& xr, const Tile& T, const bf16* wq, const float* lv, float eps,
+                                         bf16* Q, float* mean, float* rstd, bf16* q, int lane) {
+  Raw<D> r;
+  fwd_in_q_x<D>(xr, T, wq, lv, eps, Q, mean, rstd, q, lane, r);
+}
+// one half of kv (h = 0: k = x Wk^T + bk, h = 1: v = x Wv^T + bv; w: that half's image) -> kv[:, hD:(h+1)D] and r
+// (rounded as stored)
+template <int D>
+__device__ __forceinline__ void fwd_in_kv_half(const Raw<D>& xr, const Tile& T, const bf16* w, const float* lv, bf16* kv,
+                                               int h, int lane, Raw<D>& r) {
+  const int g = lane >> 4;
+  Act<D> acc;
+  zero<D>(acc);
+  mm<D>(w, xr, acc, lane);
+#pragma unroll
+  for (int j = 0; j < Lay<D>::J; ++j) acc.v[j] += vec4<D>(lv + (3 + h) * D, j, g);
+  round_act<D>(acc, r);
+  store_raw<D>(kv + h * D, 2 * D, T.m, T.ok, r, g);
+}
+// the same for two tiles at once (mm2)
+template <int D>
+__device__ __forceinline__ void fwd_in_kv_half2(const Raw<D>& x0, const Raw<D>& x1, const Tile& T0, const Tile& T1,
+                                                const bf16* w, const float* lv, bf16* kv, int h, int lane, Raw<D>& r0,
+                                                Raw<D>& r1) {
+  const int g = lane >> 4;
+  Act<D> a0, a1;
+  zero<D>(a0);
+  zero<D>(a1);
+  mm2<D>(w, x0, x1, a0, a1, lane);
+#pragma unroll
+  for (int j = 0; j < Lay<D>::J; ++j) {
+    a0.v[j] += vec4<D>(lv + (3 + h) * D, j, g);
+    a1.v[j] += vec4<D>(lv + (3 + h) * D, j, g);
+  }
+  round_act<D>(a0, r0);
+  round_act<D>(a1, r1);
+  store_raw<D>(kv + h * D, 2 * D, T0.m, T0.ok, r0, g);
+  store_raw<D>(kv + h * D, 2 * D, T1.m, T1.ok, r1, g);
 }
 // k, v = x Wk^T + bk, x Wv^T + bv -> kv [M][2D]
 template <int D>
 __device__ __forceinline__ void fwd_in_kv(const Raw<D>& xr, const Tile& T, const bf16* wk, const bf16* wv,
                                           const float* lv, bf16* kv, int lane) {
-  const int g = lane >> 4;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    Act<D> acc;
-    zero<D>(acc);
-    mm<D>(h == 0 ? wk : wv, xr, acc, lane);
-#pragma unroll
-    for (int j = 0; j < Lay<D>::J; ++j) acc.v[j] += vec4<D>(lv + (3 + h) * D, j, g);
     Raw<D> r;
-    round_act<D>(acc, r);
-    store_raw<D>(kv + h * D, 2 * D, T.m, T.ok, r, g);
+    fwd_in_kv_half<D>(xr, T, h == 0 ? wk : wv, lv, kv, h, lane, r);
   }
 }
 
@@ -1295,6 +1357,11 @@ __global__ __launch_bounds__(NT) void block_out_head_bwd_kernel(TurnArgs k) {
   }
 }
 
+// block_in_attn.hip includes this file for the device code above (RC_DEVICE_ONLY): the launchers and the entry points
+// below belong to this translation unit alone
+#ifdef RC_DEVICE_ONLY
+}  // namespace rc
+#else
 // ------------------------------------------------------------------ launch geometry
 static int g_ncu = 0;
 static int64_t grid_for(int64_t M) {
@@ -1529,3 +1596,4 @@ int rs_transpose_bf16(int64_t nmat, const int64_t* desc, int64_t max_tiles, cons
 }
 
 }  // extern "C"
+#endif  // RC_DEVICE_ONLY

@@ -10,6 +10,8 @@ bf16 fused step (FusedTrainStep, d in {64, 128}: the benchmarked path) -- per bl
 direction (rowchain.hip: one workgroup per CU, the block's three d x d weights in LDS, each wave carrying 16-token
 tiles through the sublayer chain in registers) around the LDS-resident attention (attention_lds.hip):
   x = emb*sqrt(d)+pos, drop, mask;  Q = LN1(x);      rs_sas_block_in (first block: with rs_sas_embed_args)
+                                                     (one head, two or more attention workgroups per sequence: the
+                                                     first block's chain and attention in rs_sas_block_in_attn)
   q = Q Wq^T+bq;  kv = x Wkv^T+bkv                   (same launch; sas.py:59-67, 73-76)
   o = attn(q, k, v) causal, dropout on P             rs_attn_fwd (mask_kind 0; sas.py:75)
   x1 = Q + o Wo^T + bo;  z = LN2(x1);                rs_sas_block_out (sas.py:75-84, PointWiseFeedForward)
@@ -288,6 +290,9 @@ class SASEngine:
         # the forward/backward turnaround launch (rs_sas_block_out_head_bwd: the last block's output chain, the head
         # and that block's output-side backward in one kernel); RS_SAS_TURNAROUND_FUSE=0 selects the two launches
         self.turnaround_fuse = os.environ.get("RS_SAS_TURNAROUND_FUSE", "1") != "0"
+        # block 0's input chain and attention forward in one launch (rs_sas_block_in_attn) where it applies;
+        # RS_SAS_IN_ATTN_FUSE=0 selects the two launches
+        self.in_attn_fuse = os.environ.get("RS_SAS_IN_ATTN_FUSE", "1") != "0"
         salt0 = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.salt = {"emb": site_salt(salt0, 0)}
         for i in range(self.L):
@@ -468,7 +473,16 @@ class SASEngine:
                     self.salt[f"ffn1_{i}"], self.salt[f"ffn2_{i}"], sb)
 
         ln_w, ln_b, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv = in_args(0)
-        if emb is not None:
+        # block 0's input chain and its attention forward in one launch (rs_sas_block_in_attn) where the attention
+        # launch would be the LDS kernel with two or more workgroups per sequence and the count slots cover its grid
+        in_attn = False
+        if emb is not None and self.in_attn_fuse and H == 1:
+            ns = ops.sas_block_in_attn_nsplit(d, B, T)
+            in_attn = ns >= 2 and (emb[-1] is None or emb[-1].numel() >= ns * B)
+        if in_attn:
+            ops.sas_block_in_attn(*emb, ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv, lay[0]["o"],
+                                  lay[0]["lse"], 1.0 / math.sqrt(Dh), self.salt["attn0"])
+        elif emb is not None:
             ops.sas_block_in_embed(*emb, ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv)
         else:
             ops.sas_block_in(x, ln_w, ln_b, LN_EPS, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv)
@@ -477,8 +491,9 @@ class SASEngine:
         xs = [x]
         for i in range(L):
             b = lay[i]
-            ops.attn_fwd(B, T, H, Dh, b["q"], b["kv"][:, :d], b["kv"][:, d:], b["o"], b["lse"], 1.0 / math.sqrt(Dh),
-                         0, ids, p, self.salt[f"attn{i}"], sb)
+            if i > 0 or not in_attn:
+                ops.attn_fwd(B, T, H, Dh, b["q"], b["kv"][:, :d], b["kv"][:, d:], b["o"], b["lse"],
+                             1.0 / math.sqrt(Dh), 0, ids, p, self.salt[f"attn{i}"], sb)
             if i + 1 < L:
                 ln_w, ln_b, Q, mu1, r1, Wq, bq, q, Wkv, bkv, kv = in_args(i + 1)
                 if self.boundary_fuse:

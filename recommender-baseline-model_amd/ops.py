@@ -613,6 +613,27 @@ def sas_block_in_embed(ids, T, item_emb, pos_emb, scale, drop_p, salt, seed_base
     call("rs_sas_block_in", d, C.byref(a), stream())
 
 
+def sas_block_in_attn_nsplit(d, B, T):
+    """Workgroups per sequence of sas_block_in_attn for (d, B, T); 0 where it does not cover the shape."""
+    return int(_lib.lib().rs_sas_block_in_attn_nsplit(d, B, T))
+
+
+def sas_block_in_attn(ids, T, item_emb, pos_emb, scale, drop_p, salt, seed_base, x0, count_ids, count_parts,
+                      ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv, o, lse, attn_scale, attn_salt):
+    """sas_block_in_embed(...) + attn_fwd(q, k, v -> o, lse; one head, causal, dropout drop_p with attn_salt) in one
+    launch (block_in_attn.hip), bit for bit; every slot of count_parts is written."""
+    M, d = x0.shape
+    assert ids.numel() == M and M % T == 0 and item_emb.dtype == torch.bfloat16 and x0.dtype == torch.bfloat16
+    if count_parts is not None:
+        assert count_parts.dtype == torch.int32
+    e = _sas_args(_lib.SasEmbedArgs, ids=ids, item_emb=item_emb, pos_emb=pos_emb, T=T, scale=scale, drop_p=drop_p,
+                  salt=salt, seed_base=seed_base, x0=x0, count_ids=count_ids, count_parts=count_parts)
+    a = _sas_in(x0, ln_w, ln_b, eps, Q, mean, rstd, Wq, bq, q, Wkv, bkv, kv, embed=e)
+    k = _sas_args(_lib.SasInAttnArgs, B=M // T, o=o, lse=lse, scale=attn_scale, drop_p=drop_p, salt=attn_salt,
+                  ncount=0 if count_parts is None else count_parts.numel(), **{"in": a})
+    call("rs_sas_block_in_attn", d, C.byref(k), stream())
+
+
 def sas_block_out_head(out_args, E, pos, neg, lnl_w, lnl_b, count_parts, divisor, f, pl, nl, dpl, dnl, dx, lnpart,
                        part):
     """sas_block_out(*out_args) for the last block with the SAS head in the same launch (rowchain);

@@ -209,6 +209,16 @@ def main():
             (qq, dqkv, dx1, x, m1_, r1_, gam, WinT), z, part,
             (ids, h1, x1, m1_, r1_, gam, WT, WT, WT, dy2, da1, dx1, do_, part2, a.drop, 3, 4, sb, None, None)),
             12 * mb)
+        # the first block's embed-form input chain, then the attention forward, against both in one kernel
+        if H == 1 and ops.sas_block_in_attn_nsplit(d, B, T) > 0:
+            x0 = rn(M, d)
+            cnt0 = torch.zeros(max(ops.sas_block_grid(M), ops.sas_block_in_attn_nsplit(d, B, T) * B),
+                               dtype=torch.int32, device=dev)
+            eargs = (ids, T, table, pe, math.sqrt(d), a.drop, 5, sb, x0, pos, cnt0, gam, bet, 1e-8, Q, m1_, r1_,
+                     Win[:d], bin_[:d], qq, Win[d:], bin_[d:], kvb)
+            run("fused block_in_embed", lambda: ops.sas_block_in_embed(*eargs), 5 * mb)
+            run("fused block_in_attn", lambda: ops.sas_block_in_attn(*eargs, oo, lse, 1 / math.sqrt(d), 9), 6 * mb,
+                aflops)
         # the forward/backward turnaround: block_out with the head, then block_out_bwd, against both in one kernel
         Gb = ops.sas_block_grid(M)
         cntp = torch.full((Gb,), M // Gb, dtype=torch.int32, device=dev)
