@@ -702,6 +702,39 @@ int rs_sgd_step(int64_t n, float* p, float* g, float* buf, void* p_bf16, double*
                 int zero_grad, int prepare, const float* grad_divisor, uint64_t* seed_base, const int64_t* tdesc,
                 int ntd, int64_t tbase, void* wT, const float* loss_sum, float* loss_out, int max_wg, void* stream);
 
+/* Global gradient norm and clip coefficient (gradnorm.hip): torch.nn.utils.clip_grad_norm_(parameters, max_norm,
+ * error_if_nonfinite=False) for a step whose backward and optimizer are one captured launch sequence.  The partial
+ * launches write double partial sums of squares into consecutive slots of one workspace, rs_gradnorm_finish reduces
+ * them; everything accumulates in double (the square of an fp32 is exact there).  The arithmetic of a range / list is
+ * fixed by its length alone: max_wg (>= 1) only bounds the launch's workgroups and changes no bit, and the same
+ * inputs give the same bits run to run, eager or replayed.  No allocation, no synchronisation, no atomics.
+ * rs_gradnorm_dense: ranges (HOST int64 [nranges][2], 1 <= nranges <= 8) = {lo, hi} element ranges of g (16-byte
+ * aligned, lo % 4 == 0, hi > lo; inside the buffer: the caller's promise); 16-byte loads and a scalar tail of
+ * (hi - lo) % 4 elements.  Range r writes rs_gradnorm_dense_parts(hi - lo) slots (at most 2048), the ranges' slots
+ * back to back from partials[0].
+ * rs_gradnorm_rows: the rows rows[0 .. min(*count, cap)) (rs_unique_rows' list and device count) of the table [R][d]
+ * whose row 0 g points at, d >= 1 (a bias vector is a d = 1 table); no other row is read; an id outside
+ * [0, table_rows) is skipped.  16-byte loads when d % 4 == 0 and g is 16-byte aligned, else element by element.
+ * Writes ALL rs_gradnorm_rows_parts(d, cap) slots (at most 1024) every launch, zeros where the list is short.
+ * cap * d < 2^31.
+ * rs_gradnorm_finish: s = the sum of partials[0 .. nparts) (nparts <= 2^24), norm = sqrt(s) / *div (div NULL: 1),
+ * coef = float(*max_norm / (norm + 1e-6)) clamped at 1 (torch's formula; *max_norm a device double, so it may change
+ * between graph replays; +inf never clips), record (device float[3]) = {norm, coef, effective divisor}: the divisor
+ * is *div itself (bit for bit) when coef == 1, else *div * (norm + 1e-6) / *max_norm -- the optimizer entries take
+ * &record[2] as their grad_divisor.  A non-finite sum gives coef 0 or NaN, which is applied; the record reports the
+ * norm.
+ * RS_ERR_ARG before any launch: NULL or misaligned g / partials / max_norm / record, nranges outside [1, 8], a range
+ * with hi <= lo or lo % 4, d < 1, table_rows < 1, cap < 1, cap * d >= 2^31, max_wg < 1, nparts < 1.  The *_parts
+ * helpers return -1 for such arguments. */
+int64_t rs_gradnorm_dense_parts(int64_t n);
+int64_t rs_gradnorm_rows_parts(int64_t d, int64_t cap);
+int rs_gradnorm_dense(const float* g, const int64_t* ranges, int nranges, int max_wg, double* partials,
+                      void* stream);
+int rs_gradnorm_rows(const float* g, int64_t d, int64_t table_rows, const int32_t* rows, const int32_t* count,
+                     int64_t cap, int max_wg, double* partials, void* stream);
+int rs_gradnorm_finish(const double* partials, int64_t nparts, const float* div, const double* max_norm,
+                       float* record, void* stream);
+
 /* Batched bf16 transpose: for m < nmat, desc[6m..6m+5] = {rows, cols, src_off, lds, dst_off, ldd}
  * (elements): dst[dst_off + c*ldd + r] = src[src_off + r*lds + c].  Grid x = max_tiles >= the
  * largest ceil(rows/64)*ceil(cols/64). */

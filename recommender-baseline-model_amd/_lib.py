@@ -162,6 +162,11 @@ SIGNATURES = {
     "rs_unique_rows": [vp, i64, vp, i64, vp, i64, i64, vp, vp, i64, vp, i64, vp],
     "rs_adam_rows": [i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     "rs_sgd_step": [i64, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, i32, vp],
+    "rs_gradnorm_dense_parts": [i64],
+    "rs_gradnorm_rows_parts": [i64, i64],
+    "rs_gradnorm_dense": [vp, C.POINTER(i64), i32, i32, vp, vp],
+    "rs_gradnorm_rows": [vp, i64, i64, vp, vp, i64, i32, vp, vp],
+    "rs_gradnorm_finish": [vp, i64, vp, vp, vp, vp],
     "rs_sas_block_grid": [i64],
     "rs_sas_block_boundary_fused": [i64, i64],
     "rs_sas_block_in": [i64, C.POINTER(SasInArgs), vp],
@@ -237,6 +242,7 @@ SIGNATURES = {
 RESTYPES = {"rs_wgrad_grouped_slab_numel": C.c_int64, "rs_abi_sizeof": C.c_int64,
             "rs_touched_rows_ws_numel": C.c_int64, "rs_item_index_ws_bytes": C.c_int64,
             "rs_unique_rows_ws_bytes": C.c_int64,
+            "rs_gradnorm_dense_parts": C.c_int64, "rs_gradnorm_rows_parts": C.c_int64,
             "rs_vocab_ce_ws_numel": C.c_int64, "rs_full_ws_bytes": C.c_int64,
             "rs_sas_block_grid": C.c_int64, "rs_layernorm_bwd_nparts": C.c_int64,
             "rs_sas_ce_rows_nparts": C.c_int64, "rs_sas_sce_max_k": C.c_int64,

@@ -789,6 +789,88 @@ def adam_rows(rows, count, p, g, m, v, p_bf16, state, hyper, zero_grad=False, ma
          ptr(state), ptr(hyper), int(zero_grad), int(max_wg or 8192), stream())
 
 
+# ---- global gradient norm and clip coefficient (gradnorm.hip) --------------------------------
+def gradnorm_dense_parts(n):
+    """Partial slots rs_gradnorm_dense writes for one range of n elements."""
+    k = int(_lib.lib().rs_gradnorm_dense_parts(int(n)))
+    if k < 0:
+        raise ValueError(f"gradnorm_dense_parts: a range needs n > 0, got {n}")
+    return k
+
+
+def gradnorm_rows_parts(d, cap):
+    """Partial slots rs_gradnorm_rows writes for a list of capacity cap over rows of width d."""
+    k = int(_lib.lib().rs_gradnorm_rows_parts(int(d), int(cap)))
+    if k < 0:
+        raise ValueError(f"gradnorm_rows_parts: needs d >= 1, cap >= 1 and cap * d < 2^31, got d={d}, cap={cap}")
+    return k
+
+
+def _gradnorm_partials(partials, need, who):
+    if not isinstance(partials, torch.Tensor) or partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise ValueError(f"{who}: partials must be a contiguous float64 tensor")
+    if partials.numel() < need:
+        raise ValueError(f"{who}: partials holds {partials.numel()} slots, the launch writes {need}")
+
+
+def gradnorm_dense(g, ranges, partials, max_wg=8192):
+    """Double partial sums of squares of g[lo:hi] for every (lo, hi) of `ranges` (at most 8; lo % 4 == 0) into
+    partials[0:k], range after range; returns k = sum of gradnorm_dense_parts(hi - lo).  g: contiguous fp32, 1-D."""
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.dim() != 1 or not g.is_contiguous():
+        raise ValueError("gradnorm_dense: g must be a contiguous 1-D fp32 tensor")
+    ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+    if not 1 <= len(ranges) <= 8:
+        raise ValueError(f"gradnorm_dense takes one to eight ranges, got {len(ranges)}")
+    for lo, hi in ranges:
+        if lo < 0 or lo % 4 or hi <= lo or hi > g.numel():
+            raise ValueError(f"gradnorm_dense: range ({lo}, {hi}) is empty, outside g or starts off a multiple of 4")
+    if max_wg is None or int(max_wg) < 1:
+        raise ValueError("gradnorm_dense: max_wg must be positive")
+    need = sum(gradnorm_dense_parts(hi - lo) for lo, hi in ranges)
+    _gradnorm_partials(partials, need, "gradnorm_dense")
+    arr = (_lib.i64 * (2 * len(ranges)))(*[x for r in ranges for x in r])
+    call("rs_gradnorm_dense", ptr(g), arr, len(ranges), int(max_wg), ptr(partials), stream())
+    return need
+
+
+def gradnorm_rows(g, rows, count, partials, max_wg=8192):
+    """Double partial sums of squares of the rows rows[:count] (unique_rows' list) of the table g (fp32 [R, d] or [R],
+    contiguous) and of no other row, into ALL of partials[0:k] (zeros where the list is short); returns k =
+    gradnorm_rows_parts(d, rows.numel())."""
+    _i32(rows, "rows")
+    _i32(count, "count", 1)
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.dim() not in (1, 2) or not g.is_contiguous():
+        raise ValueError("gradnorm_rows: the table must be contiguous fp32 [R, d] or [R]")
+    R, d = g.shape[0], (g.shape[1] if g.dim() == 2 else 1)
+    if R < 1 or d < 1 or rows.numel() < 1:
+        raise ValueError("gradnorm_rows: empty table or list")
+    if rows.numel() * d >= 2 ** 31:
+        raise ValueError("gradnorm_rows: list capacity * row width must stay below 2^31")
+    if max_wg is None or int(max_wg) < 1:
+        raise ValueError("gradnorm_rows: max_wg must be positive")
+    need = gradnorm_rows_parts(d, rows.numel())
+    _gradnorm_partials(partials, need, "gradnorm_rows")
+    call("rs_gradnorm_rows", ptr(g), d, R, ptr(rows), ptr(count), rows.numel(), int(max_wg), ptr(partials), stream())
+    return need
+
+
+def gradnorm_finish(partials, nparts, max_norm, record, div=None):
+    """record (fp32 [>= 3]) = {norm, coef, effective divisor} from partials[:nparts]: norm = sqrt(sum) / div, coef =
+    min(1, max_norm / (norm + 1e-6)); max_norm: float64 [1] on the device; div: fp32 [1] or None (1)."""
+    nparts = int(nparts)
+    if nparts < 1:
+        raise ValueError("gradnorm_finish: nparts must be positive")
+    _gradnorm_partials(partials, nparts, "gradnorm_finish")
+    if not isinstance(max_norm, torch.Tensor) or max_norm.dtype != torch.float64 or max_norm.numel() < 1:
+        raise ValueError("gradnorm_finish: max_norm must be a float64 device tensor")
+    if not isinstance(record, torch.Tensor) or record.dtype != torch.float32 or record.numel() < 3 \
+            or not record.is_contiguous():
+        raise ValueError("gradnorm_finish: record must be a contiguous fp32 tensor of at least 3 elements")
+    if div is not None and (div.dtype != torch.float32 or div.numel() < 1):
+        raise ValueError("gradnorm_finish: div must be an fp32 device tensor")
+    call("rs_gradnorm_finish", ptr(partials), nparts, ptr(div), ptr(max_norm), ptr(record), stream())
+
+
 def ln_partial_segments(part, M, d, dgamma, dbeta, nb=None):
     """The two reduce segments of a fused kernel's LayerNorm partials (part[b][2][d], b < nb; default: the
     SAS row-block backward kernels' set count)."""

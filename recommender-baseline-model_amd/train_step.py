@@ -252,8 +252,34 @@ class FusedStepLR:
 class FusedTrainStep:
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
                  bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None,
-                 logq=None, table_optim="dense", optimizer="adam", momentum=0.0):
+                 logq=None, table_optim="dense", optimizer="adam", momentum=0.0, max_grad_norm=None):
         """model: rbm_amd SASModel or BERTModel on a CUDA device.
+        max_grad_norm: None (default: the step's launches are exactly those of a step built without the argument), or
+        a positive number c: every step clips its gradient by global norm, torch.nn.utils.clip_grad_norm_(
+        model.parameters(), c) between the backward and the optimizer -- ``grad_norm`` (the total norm BEFORE
+        clipping, what clip_grad_norm_ returns) and ``clip_coef`` = min(1, c / (norm + 1e-6)) are device scalars of
+        the last step, read without any synchronisation by the step; the optimizer kernels take the gradient divided
+        by the record's effective divisor (1 exactly when nothing is clipped, else (norm + 1e-6) / c) through their
+        grad_divisor pointer.  float("inf") measures the norm and never clips.  c lives on the device:
+        set_max_grad_norm() changes it under captured graphs.  The regulariser's gradient (l2_emb) is part of the
+        norm, as in the reference loop where it is part of the loss; weight decay is added after the scale, outside
+        it, as torch's optimizers add it.  A non-finite norm is applied as torch applies it (error_if_nonfinite=
+        False: coefficient 0 or NaN), no step is skipped.  Not optimizer state: checkpoints are unchanged.
+        Single device only: data parallel and vocab_shard are a ValueError, as are zero, a negative
+        number, NaN, a bool and a non-number.  The whole update runs at the end of the step (no early head / token
+        update).  What the norm reads, (rs_gradnorm_dense / rs_gradnorm_rows -> rs_gradnorm_finish) after the
+        regulariser and right before the optimizer, when the backward and every side branch of it have been joined:
+          dense tables     the whole flat gradient [0, numel) (the aux tail excluded).  Every parameter's gradient is
+                           complete there; alignment padding is zero in every buffer; the rows of a row-marked table
+                           that this step did not stamp were cleared by an earlier sweep and are zero in memory (the
+                           marks only spare the optimizer their loads); the `keep` range (BERT's out.weight /
+                           out.bias at V1 * d >= 2^24) is overwritten whole by this step's head backward -- exact
+                           zeros where no logit was labelled -- so it holds this step's gradient although no sweep
+                           clears it.
+          table_optim=     dense partials over the ranges beside the sparse tables (FusedAdam._sparse_segments) and
+          "sparse"         row-list partials over each table's touched-row list (one list for out.weight and
+                           out.bias): a row off the list, row 0 included, has a zero gradient by the sparse tables'
+                           contract, and is not read.
         optimizer: "adam" (default: torch.optim.Adam, BS/trainers/base.py:225-228) or "sgd" (torch.optim.SGD(params,
         lr, weight_decay=weight_decay, momentum=momentum), BS/trainers/base.py:229-233), case-insensitive as the
         reference lowercases args.optimizer.  "sgd" runs every loss of the step on one device and plain data parallel
@@ -346,6 +372,10 @@ class FusedTrainStep:
         self._logq_arg = logq
         self.logq = logq if isinstance(logq, torch.Tensor) else None
         dp_on = dpx.world() > 1 if dp is None else bool(dp)
+        self.max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        if self.max_grad_norm is not None and (dp_on or vocab_shard):
+            raise ValueError("FusedTrainStep(max_grad_norm=...) runs on a single device (data parallel and "
+                             "vocab_shard are not covered: the norm would have to follow the gradient exchange)")
         if table_optim not in ("dense", "sparse"):
             raise ValueError(f"table_optim must be 'dense' or 'sparse', got {table_optim!r}")
         self.table_optim = table_optim
@@ -414,6 +444,14 @@ class FusedTrainStep:
         self.count = torch.zeros(1, dtype=torch.float32, device=dev)
         self.one = torch.ones(1, dtype=torch.float32, device=dev)
         self.loss_val = torch.zeros(1, dtype=torch.float32, device=dev)
+        # gradient clipping: the bound (a device double, as the optimizers' hyper[0] is for set_lr), the step's
+        # record {norm, coef, effective divisor} and the partial sums' workspace (sized by the first step)
+        self.grad_norm = self.clip_coef = None
+        if self.max_grad_norm is not None:
+            self._clip_max = torch.tensor([self.max_grad_norm], dtype=torch.float64, device=dev)
+            self._clip_rec = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.grad_norm, self.clip_coef = self._clip_rec[0], self._clip_rec[1]
+            self._clip_ws = None
         self.graphs = None
         self.static = None
         self.steps_per_graph = 1
@@ -462,9 +500,10 @@ class FusedTrainStep:
         self._early_forked = False     # this step forked an early update that _update has yet to join
         # Not with the sampled-softmax head: it accumulates into a zeroed out.weight / out.bias gradient (no
         # overwritten range), and its index launches finish on the side stream only at the end of the backward.
-        # Nor under SGD: its whole update runs at the end of the step.
+        # Nor under SGD: its whole update runs at the end of the step.  Nor with gradient clipping: no update can run
+        # before the whole gradient's norm is known.
         self._early_ok = (self.kind == "bert" and self.loss != "sampled_ce" and not self.dp and self.vshard is None
-                          and self.optimizer == "adam"
+                          and self.optimizer == "adam" and self.max_grad_norm is None
                           and not self.l2
                           and os.environ.get("RS_EARLY_HEAD_ADAM", "1") != "0"
                           and hasattr(self.engine, "overwritten_grads"))
@@ -747,7 +786,52 @@ class FusedTrainStep:
             else:
                 self._l2(self.loss_out[2:3])
                 sp = self._sparse_spec() if self._sparse_tables is not None else None
-                self.opt.step(seed_base=sb, transposed=tr, keep=kp, sparse=sp)
+                if self.max_grad_norm is None:
+                    self.opt.step(seed_base=sb, transposed=tr, keep=kp, sparse=sp)
+                else:
+                    self.opt.step(grad_divisor=self._clip_norm(sp), seed_base=sb, transposed=tr, keep=kp, sparse=sp)
+
+    @staticmethod
+    def _check_max_grad_norm(c):
+        if c is None:
+            return None
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or math.isnan(c) or c <= 0:
+            raise ValueError(f"max_grad_norm must be a positive number (float('inf'): measure, never clip) or None, "
+                             f"got {c!r}")
+        return float(c)
+
+    def set_max_grad_norm(self, c):
+        """Change the clipping bound of a step built with max_grad_norm: it lives on the device, so captured graphs
+        replayed afterwards clip by it without re-capture (as FusedAdam.set_lr)."""
+        if self.max_grad_norm is None or c is None:
+            raise ValueError("set_max_grad_norm needs a step built with max_grad_norm (the norm's launches are part "
+                             "of its graphs), and a number")
+        self.max_grad_norm = self._check_max_grad_norm(c)
+        self._clip_max[0] = self.max_grad_norm
+
+    def _clip_norm(self, sparse):
+        """The step's gradient norm, coefficient and effective divisor (grad_norm / clip_coef / the returned fp32 [1]
+        view, which the optimizer takes as its grad_divisor): partial launches over the ranges named in __init__'s
+        docstring (max_grad_norm), then the finish launch, on the current stream.  sparse: this step's
+        FusedAdam.step `sparse`."""
+        f = self.flat
+        segs = [(lo, hi) for lo, hi, _ in self.opt._sparse_segments(sparse)] if sparse else [(0, f.numel)]
+        sizes = [sum(ops.gradnorm_dense_parts(hi - lo) for lo, hi in segs)] if segs else [0]
+        sizes += [ops.gradnorm_rows_parts(d, lst.numel()) for _, _, d, lst, _ in sparse or ()]
+        if self._clip_ws is None or self._clip_ws.numel() != sum(sizes):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the gradient norm's workspace must be allocated by an eager step before a capture")
+            self._clip_ws = torch.zeros(sum(sizes), dtype=torch.float64, device=f.device)
+        ws = self._clip_ws
+        if segs:
+            ops.gradnorm_dense(f.grad[:f.numel], segs, ws)
+        at = sizes[0]
+        for (lo, rows, d, lst, cnt), k in zip(sparse or (), sizes[1:]):
+            g = f.grad[lo:lo + rows * d]
+            ops.gradnorm_rows(g.view(rows, d) if d > 1 else g, lst, cnt, ws[at:at + k])
+            at += k
+        ops.gradnorm_finish(ws, at, self._clip_max, self._clip_rec)
+        return self._clip_rec[2:3]
 
     def _post_update(self):
         """Sharded item table: all-gather the updated compute rows; the other ranks' master rows are stale now."""
