@@ -30,7 +30,7 @@ import torch
 from . import dp as dpx
 from . import ops
 from .engine_util import SideBranch, release_capture_events
-from .flat import ALIGN
+from .optim import FusedAdam, FusedSGD, FusedStepLR, plan  # noqa: F401 (the optimizers stay importable from here)
 
 
 # thread-local capture: the process group's watchdog thread polls its collectives' events while a step graph is
@@ -38,218 +38,84 @@ from .flat import ALIGN
 CAPTURE_MODE = "thread_local"
 
 
-class FusedAdam:
-    """Device-side torch.optim.Adam over a FlatParams buffer (rs_adam_prepare_step / rs_adam_step)."""
-
-    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        dev = flat.device
-        self.flat = flat
-        self.m = torch.zeros(flat.numel, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(flat.numel, dtype=torch.float32, device=dev)
-        # [t, lr/bc1, sqrt(bc2), grad scale, -, -, -, arrival counters of rs_adam_prepare_step (state[7],
-        # state[16 + 16 k], k < 8)]
-        self.state = torch.zeros(144, dtype=torch.float64, device=dev)
-        self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float64, device=dev)
-        self.weight_decay = float(weight_decay)     # host copy: step(sparse=...) refuses a non-zero decay
-        # (table lo, rows, log2 d, row marks, epoch): a table whose gradient rows only the marked item gradient
-        # writes -- the sweep skips the gradient loads of the rows it did not stamp (rs_adam_*_marked)
-        self.marks = None
-
-    def _marks(self, lo, hi):
-        if self.marks is None:
-            return None
-        tlo, rows, dshift, rm, ep = self.marks
-        if hi <= tlo or lo >= tlo + (rows << dshift):
-            return None
-        return rm, ep, tlo - lo, rows, dshift
-
-    def set_lr(self, lr):
-        """StepLR hook (BS/trainers/base.py:40,87): lives on the device, so graph replays see it."""
-        self.hyper[0] = lr
-
-    def _sparse_segments(self, sparse):
-        """The dense launches' ranges beside the sparse tables: the complement of the tables in the flat buffer.  A
-        table's range runs to the end of its alignment padding (FlatParams.ALIGN), whose elements are zero in every
-        buffer and stay so under either rule, so each dense range starts 16-byte aligned."""
-        f = self.flat
-        if self.weight_decay != 0.0:
-            raise ValueError("sparse tables need weight_decay == 0: the decay has no meaning for a skipped row")
-        cuts = []
-        for lo, rows, d, lst, cnt in sparse:
-            lo, n = int(lo), int(rows) * int(d)
-            if lo % ALIGN or lo < 0 or n <= 0 or lo + n > f.numel:
-                raise ValueError(f"sparse table (lo={lo}, rows={rows}, d={d}) is not a parameter of the flat buffer")
-            cuts.append((lo, min(lo + -(-n // ALIGN) * ALIGN, f.numel)))
-        cuts.sort()
-        segs, a = [], 0
-        for lo, hi in cuts + [(f.numel, f.numel)]:
-            if lo < a:
-                raise ValueError("sparse tables overlap")
-            if lo > a:
-                segs.append((a, lo, True))
-            a = hi
-        return segs
-
-    def step(self, grad_divisor=None, seed_base=None, ranges=None, transposed=None, loss=None, keep=None,
-             sparse=None):
-        """One Adam update; also clears the gradient buffer (the next step accumulates from zero) and
-        advances the dropout step seed when given.  ranges: [(lo, hi)] flat slices to update (default all; a
-        vocabulary-sharded rank skips the output rows other ranks own).  loss = (sum, out): out = sum / grad_divisor
-        in the first launch.  transposed (the SAS block weights' transposed bf16 copies) rides in the first range's
-        launch, which must cover those matrices.  keep = (lo, hi): a slice the backward OVERWRITES every step
-        (BERT's out.weight / out.bias with a large vocabulary): updated by its own launch that leaves its gradient
-        in place -- no zero written by this sweep, none read back by the next step's dE GEMM (2 GB per step at 1M
-        items).
-
-        sparse = [(lo, rows, d, rows_list, count)]: tables [rows][d] at flat offset lo that take the LAZY rule: only
-        the rows rows_list[:count] (ops.unique_rows: int32 device list and count, distinct ids) are updated, by
-        rs_adam_rows after the preparing launch, with the dense sweep's arithmetic and this step's scalars (one
-        global step count, advanced once); every other row of p / m / v / the bf16 copy stays bit for bit, and its
-        gradient (zero by contract) is neither read nor written.  The dense launches cover the rest of the buffer.
-        With every row listed every step this equals the dense step bit for bit.  Against torch.optim.SparseAdam
-        the rule differs only in where eps sits: the dense kernel's denom = sqrt(v) / sqrt(bc2) + eps with step size
-        lr / bc1 is kept, where SparseAdam forms sqrt(v) + eps and folds sqrt(bc2) into the step size.  Needs
-        weight_decay == 0 (ValueError), and neither ranges nor keep."""
-        f = self.flat
-        if sparse:
-            if ranges is not None or keep is not None:
-                raise ValueError("sparse tables go with neither ranges nor keep")
-            segs = self._sparse_segments(sparse)
-            if not segs:     # nothing dense: the step's scalars by their own launch
-                ops.adam_prepare(self.state, self.hyper, grad_divisor, seed_base)
-        else:
-            segs = [(lo, hi, True) for lo, hi in (ranges or [(0, f.numel)])]
-        if keep is not None and ranges is None:
-            klo, khi = keep
-            assert 0 < klo < khi <= f.numel and klo % 4 == 0 and khi % 4 == 0, keep
-            segs = [(0, klo, True), (klo, khi, False)] + ([(khi, f.numel, True)] if khi < f.numel else [])
-        for k, (lo, hi, zg) in enumerate(segs):
-            bf = f.bf16[lo:hi] if f.bf16 is not None else None
-            if k == 0:   # the first range's launch also prepares the step's scalars (rs_adam_prepare_step)
-                ops.adam_prepare_step(f.data[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], bf, self.state,
-                                      self.hyper, zero_grad=zg, grad_divisor=grad_divisor, seed_base=seed_base,
-                                      transposed=transposed, tbase=lo,
-                                      loss_sum=loss[0] if loss else None, loss_out=loss[1] if loss else None,
-                                      marks=self._marks(lo, hi))
-            else:
-                ops.adam_step(f.data[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], bf, self.state,
-                              self.hyper, zero_grad=zg, marks=self._marks(lo, hi))
-        for lo, rows, d, lst, cnt in sparse or ():
-            hi = lo + rows * d
-            shp = (rows, d) if d > 1 else (rows,)
-            bf = f.bf16[lo:hi].view(shp) if f.bf16 is not None else None
-            ops.adam_rows(lst, cnt, f.data[lo:hi].view(shp), f.grad[lo:hi].view(shp), self.m[lo:hi].view(shp),
-                          self.v[lo:hi].view(shp), bf, self.state, self.hyper, zero_grad=True)
-
-    def step_keep_early(self, keep, max_wg=None, zero_grad=False):
-        """The first part of a step whose `keep` range is final before the rest of the backward (BERT's out.weight /
-        out.bias, after the head's dE / dh): rs_adam_prepare (t += 1 and the step's scalars; no seed advance -- the
-        backward still draws this step's dropout masks) and that range's update, gradient left in place.
-        step_rest() finishes the step: the same per-element math as step(keep=...), bit for bit."""
-        lo, hi = keep
-        f = self.flat
-        ops.adam_prepare(self.state, self.hyper)
-        bf = f.bf16[lo:hi] if f.bf16 is not None else None
-        ops.adam_step(f.data[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], bf, self.state, self.hyper,
-                      zero_grad=zero_grad, max_wg=max_wg, marks=self._marks(lo, hi))
-
-    def step_range(self, lo, hi, zero_grad=True, max_wg=None):
-        """rs_adam_step over [lo, hi) with the step's scalars already prepared (a step_keep_early step)."""
-        f = self.flat
-        bf = f.bf16[lo:hi] if f.bf16 is not None else None
-        ops.adam_step(f.data[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], bf, self.state, self.hyper,
-                      zero_grad=zero_grad, max_wg=max_wg, marks=self._marks(lo, hi))
-
-    def step_rest(self, keep, seed_base=None, done=()):
-        """The rest of a step_keep_early step: every range outside `keep` and the ranges in `done` (already updated
-        by step_range) with the gradient cleared, then the seed."""
-        f = self.flat
-        cuts = sorted([tuple(keep)] + [tuple(r) for r in done])
-        a = 0
-        for lo, hi in cuts + [(f.numel, f.numel)]:
-            assert lo >= a, (cuts, a)
-            if lo > a:
-                self.step_range(a, lo)
-            a = hi
-        if seed_base is not None:
-            ops.seed_advance(seed_base)
-
-
-class FusedSGD:
-    """Device-side torch.optim.SGD(params, lr, momentum=, weight_decay=) over a FlatParams buffer (rs_sgd_step): the
-    reference's other optimizer (BS/trainers/base.py:229-233; dampening 0, nesterov False).  hyper[0] is the rate, so
-    FusedStepLR drives it through set_lr as it drives FusedAdam; state[0] is the device step count."""
-
-    MAX_WG = 8192      # rs_adam_step's grid bound
-
-    def __init__(self, flat, lr, momentum=0.0, weight_decay=0.0):
-        dev = flat.device
-        self.flat = flat
-        self.momentum = float(momentum)
-        self.weight_decay = float(weight_decay)
-        # the momentum buffer, zero-initialised: torch's first-step rule (buf = grad.clone()) falls out of the update
-        self.buf = torch.zeros(flat.numel, dtype=torch.float32, device=dev) if self.momentum != 0 else None
-        self.state = torch.zeros(8, dtype=torch.float64, device=dev)
-        self.hyper = torch.tensor([lr, self.momentum, self.weight_decay], dtype=torch.float64, device=dev)
-        self.marks = None      # no row-marked sweeps under SGD
-
-    def set_lr(self, lr):
-        """StepLR hook (BS/trainers/base.py:40,87): lives on the device, so graph replays see it."""
-        self.hyper[0] = lr
-
-    def step(self, grad_divisor=None, seed_base=None, ranges=None, transposed=None, loss=None, keep=None,
-             sparse=None):
-        """One SGD update, FusedAdam.step's range semantics: ranges = [(lo, hi)] flat slices (default all); the first
-        range's launch also advances the step count and the seed and forms loss = (sum, out) (prepare=1) and carries
-        the transposed copies; keep = (lo, hi): a slice updated by its own launch that leaves its gradient in
-        place.  Every other range's gradient is cleared."""
-        if sparse:
-            raise ValueError("FusedSGD has no sparse (touched-rows-only) rule: the lazy rule is Adam's")
-        f = self.flat
-        segs = [(lo, hi, True) for lo, hi in (ranges or [(0, f.numel)])]
-        if keep is not None and ranges is None:
-            klo, khi = keep
-            assert 0 < klo < khi <= f.numel and klo % 4 == 0 and khi % 4 == 0, keep
-            segs = [(0, klo, True), (klo, khi, False)] + ([(khi, f.numel, True)] if khi < f.numel else [])
-        for k, (lo, hi, zg) in enumerate(segs):
-            first = k == 0
-            ops.sgd_step(f.data[lo:hi], f.grad[lo:hi], self.buf[lo:hi] if self.buf is not None else None,
-                         f.bf16[lo:hi] if f.bf16 is not None else None, self.state, self.hyper, zero_grad=zg,
-                         prepare=first, grad_divisor=grad_divisor, seed_base=seed_base if first else None,
-                         transposed=transposed if first else None, tbase=lo,
-                         loss_sum=loss[0] if loss and first else None, loss_out=loss[1] if loss and first else None,
-                         max_wg=self.MAX_WG)
-
-
-class FusedStepLR:
-    """``torch.optim.lr_scheduler.StepLR(optimizer, step_size, gamma)`` for a FusedAdam or FusedSGD (BS/trainers/base.py:40, stepped
-    once per epoch at :87): every ``step_size``-th ``step()`` multiplies the learning rate by ``gamma`` -- chained in
-    Python floats exactly as torch's StepLR forms it -- and writes it into the optimizer's device hyperparameters, so
-    captured step graphs replayed afterwards use it without re-capture."""
-
-    def __init__(self, optimizer, step_size, gamma=0.1):
-        self.optimizer = optimizer.opt if isinstance(optimizer, FusedTrainStep) else optimizer
-        self.step_size = int(step_size)
-        self.gamma = float(gamma)
-        self.base_lr = float(self.optimizer.hyper[0].item())
-        self.lr = self.base_lr
-        self.last_epoch = 0
-
-    def step(self):
-        self.last_epoch += 1
-        if self.last_epoch % self.step_size == 0:
-            self.lr = self.lr * self.gamma
-            self.optimizer.set_lr(self.lr)
-
-    def get_last_lr(self):
-        return [self.lr]
-
-    def state_dict(self):
-        return {"step_size": self.step_size, "gamma": self.gamma, "base_lrs": [self.base_lr],
-                "last_epoch": self.last_epoch, "_last_lr": [self.lr]}
-
-
 class FusedTrainStep:
+    def _check_args(self, weight_decay, dp, vocab_shard, shard_rows, loss, logq, table_optim, optimizer, momentum,
+                    max_grad_norm):
+        """Every refusal of __init__'s arguments, before the device is touched, in a fixed order (a call that breaks
+        two rules raises the first): optimizer and momentum, loss, logq, max_grad_norm, table_optim, the single-device
+        rules.  Returns the resolved (optimizer, momentum, shard_rows, loss, max_grad_norm, data parallel or not)."""
+        model, kind = self.model, self.kind
+        if not isinstance(optimizer, str) or optimizer.lower() not in ("adam", "sgd"):
+            raise ValueError(f"optimizer must be 'adam' or 'sgd' (the reference's args.optimizer), got {optimizer!r}")
+        optimizer = optimizer.lower()
+        if optimizer == "adam":
+            # the reference reads args.momentum in its SGD branch only, and its default is None: None (and 0) pass
+            if momentum is not None and (isinstance(momentum, bool) or momentum != 0):
+                raise ValueError(f"momentum={momentum!r} needs optimizer='sgd' (Adam takes none)")
+            momentum = 0.0
+        elif momentum is None or isinstance(momentum, bool) or not isinstance(momentum, (int, float)) \
+                or not math.isfinite(momentum) or momentum < 0:
+            raise ValueError(f"optimizer='sgd': momentum must be a finite number >= 0, got {momentum!r} (the "
+                             "reference's own default, momentum=None, makes torch.optim.SGD raise too: pass a number)")
+        momentum = float(momentum)
+        if optimizer == "sgd":
+            if table_optim == "sparse":
+                raise ValueError("table_optim='sparse' needs optimizer='adam': the lazy rule is Adam's")
+            if shard_rows == "on":
+                raise ValueError("shard_rows='on' needs optimizer='adam': the sharded item-table optimizer is not "
+                                 "covered under SGD")
+            if vocab_shard:
+                raise ValueError("vocab_shard needs optimizer='adam': the vocabulary-sharded head is not covered "
+                                 "under SGD")
+            shard_rows = "off"
+        if loss is None:
+            loss = getattr(model.sas, "sas_loss", "bce") if kind == "sas" else None
+            if kind == "bert" and getattr(model.bert, "bert_loss", "ce") == "sampled_ce":
+                loss = "sampled_ce"
+        if kind == "sas" and loss not in ("bce", "ce", "sampled_ce"):
+            raise ValueError(f"loss must be 'bce', 'ce' or 'sampled_ce', got {loss!r}")
+        if kind != "sas" and loss not in (None, "sampled_ce"):
+            raise ValueError(f"loss={loss!r} needs a SAS model (a BERT step takes loss='sampled_ce', or None for the "
+                             "model's own bert_loss: its cross-entropy by default)")
+        if isinstance(logq, torch.Tensor):
+            if loss != "sampled_ce":
+                raise ValueError(f"logq corrects the sampled softmax: it needs loss='sampled_ce' (got loss={loss!r})")
+        elif logq not in (None, False):
+            raise ValueError("logq must be a tensor, False (never correct) or None (adopt the sampler's proposal)")
+        dp_on = dpx.world() > 1 if dp is None else bool(dp)
+        max_grad_norm = self._check_max_grad_norm(max_grad_norm)
+        if max_grad_norm is not None and (dp_on or vocab_shard):
+            raise ValueError("FusedTrainStep(max_grad_norm=...) runs on a single device (data parallel and "
+                             "vocab_shard are not covered: the norm would have to follow the gradient exchange)")
+        if table_optim not in ("dense", "sparse"):
+            raise ValueError(f"table_optim must be 'dense' or 'sparse', got {table_optim!r}")
+        if table_optim == "sparse":      # every refusal before the first launch
+            why = None
+            if kind == "sas" and loss == "ce":
+                why = "loss='ce' gives every row of the item table a gradient: there is nothing to skip"
+            elif kind == "bert" and loss != "sampled_ce":
+                why = ("BERT's full cross-entropy writes a dense out.weight / out.bias gradient (and takes the "
+                       "keep / early-head optimizer path): only loss='sampled_ce' is covered")
+            elif dp_on:
+                why = "it runs on one rank (the data-parallel gradient exchange is not covered)"
+            elif vocab_shard:
+                why = "vocab_shard is not covered"
+            elif weight_decay != 0.0:
+                why = f"weight_decay must be 0 (got {weight_decay}): the decay has no meaning for a skipped row"
+            elif kind == "sas" and float(getattr(model.sas, "l2_emb", 0.0)) != 0.0:
+                why = f"l2_emb must be 0 (got {model.sas.l2_emb}): the regulariser gives every row a gradient"
+            if why:
+                raise ValueError(f"FusedTrainStep(table_optim='sparse'): {why}")
+        if loss in ("ce", "sampled_ce") and dp_on:
+            raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
+        if kind == "bert" and loss == "sampled_ce" and vocab_shard:
+            raise ValueError("FusedTrainStep(loss='sampled_ce') runs on a single device (vocab_shard is not covered)")
+        if vocab_shard and not (dp_on and kind == "bert"):
+            raise ValueError("vocab_shard needs a data-parallel BERT step")
+        if dp_on and kind == "sas" and shard_rows == "on" and float(getattr(model.sas, "l2_emb", 0.0)):
+            raise ValueError("shard_rows needs l2_emb == 0 (the regulariser reads every master row)")
+        return optimizer, momentum, shard_rows, loss, max_grad_norm, dp_on
+
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
                  bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None,
                  logq=None, table_optim="dense", optimizer="adam", momentum=0.0, max_grad_norm=None):
@@ -329,77 +195,10 @@ class FusedTrainStep:
         them (needs l2_emb == 0: the regulariser reads every master row)."""
         self.model = model
         self.kind = model.code()
-        # the optimizer switch: every refusal before the first launch and before the device is touched
-        if not isinstance(optimizer, str) or optimizer.lower() not in ("adam", "sgd"):
-            raise ValueError(f"optimizer must be 'adam' or 'sgd' (the reference's args.optimizer), got {optimizer!r}")
-        self.optimizer = optimizer.lower()
-        if self.optimizer == "adam":
-            # the reference reads args.momentum in its SGD branch only, and its default is None: None (and 0) pass
-            if momentum is not None and (isinstance(momentum, bool) or momentum != 0):
-                raise ValueError(f"momentum={momentum!r} needs optimizer='sgd' (Adam takes none)")
-            momentum = 0.0
-        elif momentum is None or isinstance(momentum, bool) or not isinstance(momentum, (int, float)) \
-                or not math.isfinite(momentum) or momentum < 0:
-            raise ValueError(f"optimizer='sgd': momentum must be a finite number >= 0, got {momentum!r} (the "
-                             "reference's own default, momentum=None, makes torch.optim.SGD raise too: pass a number)")
-        self.momentum = float(momentum)
-        if self.optimizer == "sgd":
-            if table_optim == "sparse":
-                raise ValueError("table_optim='sparse' needs optimizer='adam': the lazy rule is Adam's")
-            if shard_rows == "on":
-                raise ValueError("shard_rows='on' needs optimizer='adam': the sharded item-table optimizer is not "
-                                 "covered under SGD")
-            if vocab_shard:
-                raise ValueError("vocab_shard needs optimizer='adam': the vocabulary-sharded head is not covered "
-                                 "under SGD")
-            shard_rows = "off"
-        if loss is None:
-            loss = getattr(model.sas, "sas_loss", "bce") if self.kind == "sas" else None
-            if self.kind == "bert" and getattr(model.bert, "bert_loss", "ce") == "sampled_ce":
-                loss = "sampled_ce"
-        if self.kind == "sas":
-            if loss not in ("bce", "ce", "sampled_ce"):
-                raise ValueError(f"loss must be 'bce', 'ce' or 'sampled_ce', got {loss!r}")
-        elif loss not in (None, "sampled_ce"):
-            raise ValueError(f"loss={loss!r} needs a SAS model (a BERT step takes loss='sampled_ce', or None for the "
-                             "model's own bert_loss: its cross-entropy by default)")
-        self.loss = loss
-        if isinstance(logq, torch.Tensor):
-            if loss != "sampled_ce":
-                raise ValueError(f"logq corrects the sampled softmax: it needs loss='sampled_ce' (got loss={loss!r})")
-        elif logq not in (None, False):
-            raise ValueError("logq must be a tensor, False (never correct) or None (adopt the sampler's proposal)")
-        self._logq_arg = logq
+        self.optimizer, self.momentum, shard_rows, loss, self.max_grad_norm, self.dp = self._check_args(
+            weight_decay, dp, vocab_shard, shard_rows, loss, logq, table_optim, optimizer, momentum, max_grad_norm)
+        self.loss, self.table_optim, self._logq_arg = loss, table_optim, logq
         self.logq = logq if isinstance(logq, torch.Tensor) else None
-        dp_on = dpx.world() > 1 if dp is None else bool(dp)
-        self.max_grad_norm = self._check_max_grad_norm(max_grad_norm)
-        if self.max_grad_norm is not None and (dp_on or vocab_shard):
-            raise ValueError("FusedTrainStep(max_grad_norm=...) runs on a single device (data parallel and "
-                             "vocab_shard are not covered: the norm would have to follow the gradient exchange)")
-        if table_optim not in ("dense", "sparse"):
-            raise ValueError(f"table_optim must be 'dense' or 'sparse', got {table_optim!r}")
-        self.table_optim = table_optim
-        if table_optim == "sparse":      # every refusal before the first launch
-            why = None
-            if self.kind == "sas" and loss == "ce":
-                why = "loss='ce' gives every row of the item table a gradient: there is nothing to skip"
-            elif self.kind == "bert" and loss != "sampled_ce":
-                why = ("BERT's full cross-entropy writes a dense out.weight / out.bias gradient (and takes the "
-                       "keep / early-head optimizer path): only loss='sampled_ce' is covered")
-            elif dp_on:
-                why = "it runs on one rank (the data-parallel gradient exchange is not covered)"
-            elif vocab_shard:
-                why = "vocab_shard is not covered"
-            elif weight_decay != 0.0:
-                why = f"weight_decay must be 0 (got {weight_decay}): the decay has no meaning for a skipped row"
-            elif self.kind == "sas" and float(getattr(model.sas, "l2_emb", 0.0)) != 0.0:
-                why = f"l2_emb must be 0 (got {model.sas.l2_emb}): the regulariser gives every row a gradient"
-            if why:
-                raise ValueError(f"FusedTrainStep(table_optim='sparse'): {why}")
-        if loss in ("ce", "sampled_ce") and dp_on:
-            raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
-        if self.kind == "bert" and loss == "sampled_ce" and vocab_shard:
-            raise ValueError("FusedTrainStep(loss='sampled_ce') runs on a single device (vocab_shard is not covered)")
         self.engine = model.sas.engine() if self.kind == "sas" else model.engine()
         if self.kind == "bert":
             self.engine.loss = "sampled_ce" if loss == "sampled_ce" else "ce"
@@ -414,7 +213,6 @@ class FusedTrainStep:
         else:
             self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
         self.pg = process_group
-        self.dp = dpx.world() > 1 if dp is None else bool(dp)
         self.bucket_numel = bucket_numel
         self.overlap = self.dp and (bucket_numel is None if overlap is None else bool(overlap))
         if self.dp:
@@ -427,8 +225,6 @@ class FusedTrainStep:
         self.vshard = None
         if vocab_shard:
             from .vocab_parallel import VocabShard
-            if not (self.dp and self.kind == "bert"):
-                raise ValueError("vocab_shard needs a data-parallel BERT step")
             self.vshard = VocabShard(self.flat.shapes["out.weight"][0], self.pg)
             self.engine.vocab_shard = self.vshard
             self.overlap = True
@@ -461,15 +257,11 @@ class FusedTrainStep:
         # gloo with two ranks only (one GPU reaches this builder, and RCCL refuses two ranks on one device), so the
         # sharded form is an explicit opt-in there until a multi-GPU run pins it to the dense exchange
         auto_ok = dpx.backend(self.pg) != "nccl" if self.dp else False
-        if self.dp and self.kind == "sas" and shard_rows != "off":
+        if self.dp and self.kind == "sas" and shard_rows != "off" and not self.l2:      # ("on" with l2_emb: refused)
             name = "item_emb.weight"
             n = self.flat.view(name).numel()
             if shard_rows == "on" or (auto_ok and dpx.ShardedRows.worthwhile(n, dpx.world(self.pg))):
-                if self.l2:
-                    if shard_rows == "on":
-                        raise ValueError("shard_rows needs l2_emb == 0 (the regulariser reads every master row)")
-                else:
-                    self.rshard = dpx.ShardedRows(self.flat, name, self.pg)
+                self.rshard = dpx.ShardedRows(self.flat, name, self.pg)
         self.exchange = None
         if self.overlap:
             b, extra = self._buckets(), None
@@ -503,8 +295,7 @@ class FusedTrainStep:
         # Nor under SGD: its whole update runs at the end of the step.  Nor with gradient clipping: no update can run
         # before the whole gradient's norm is known.
         self._early_ok = (self.kind == "bert" and self.loss != "sampled_ce" and not self.dp and self.vshard is None
-                          and self.optimizer == "adam" and self.max_grad_norm is None
-                          and not self.l2
+                          and self.optimizer == "adam" and self.max_grad_norm is None and not self.l2
                           and os.environ.get("RS_EARLY_HEAD_ADAM", "1") != "0"
                           and hasattr(self.engine, "overwritten_grads"))
         self._opt_side = SideBranch(dev, avoid=[self.engine.side.stream]) if self._early_ok else None
@@ -528,14 +319,15 @@ class FusedTrainStep:
         tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce")
         # A sparse table takes no marks either: its untouched rows are not swept at all.
         sparse = table_optim == "sparse"
-        sgd = self.optimizer == "sgd"       # the marked sweeps are Adam's: marks stay off under SGD
-        if tied_head or sparse or sgd:
+        no_marks = tied_head or sparse or self.optimizer == "sgd"       # (the marked sweeps are Adam's)
+        if no_marks:
             self.engine.row_marks = None
         # sparse tables: [(key positions in the batch, [(flat offset, rows, d)])] -- one union list per entry, shared
         # by its tables (out.weight and out.bias); the lists and their workspaces are allocated by the first step
         self._sparse_tables = None
         self._sparse_bufs = None
         self._rows_side = None
+        self._rows_forked = False      # this step forked the touched-row lists' build: _sparse_spec has yet to join it
         if sparse:
             f = self.flat
 
@@ -548,7 +340,7 @@ class FusedTrainStep:
                 self._sparse_tables = [((0,), [tab("bert.embedding.token.weight")]),
                                        ((1, 2), [tab("out.weight"), tab("out.bias")])]
             self._rows_side = SideBranch(dev, avoid=taken + [self._capture_side.stream])
-        if (not self.dp and not self.l2 and not tied_head and not sparse and not sgd
+        if (not self.dp and not self.l2 and not no_marks
                 and os.environ.get("RS_ROW_MARKS", "1") != "0"
                 and hasattr(self.engine, "enable_row_marks")):
             r = self.engine.enable_row_marks(self.ROW_MARKS_MIN)
@@ -652,7 +444,7 @@ class FusedTrainStep:
 
     def _sparse_spec(self):
         """FusedAdam.step's `sparse` for this step: joins the rows branch first."""
-        if not getattr(self, "_rows_forked", False):
+        if not self._rows_forked:
             raise RuntimeError("table_optim='sparse': the optimizer needs the step's touched-row lists (_compute "
                                "with update=True builds them)")
         self._rows_side.join()
@@ -769,10 +561,9 @@ class FusedTrainStep:
                 if self.l2:
                     torch.div(lsum, cnt, out=self.loss_val)
                     self._l2(self.loss_val, scale=cnt)
-                    self.opt.step(grad_divisor=cnt, seed_base=sb, transposed=tr, keep=kp, ranges=rg)
-                else:   # the loss division rides in the optimizer's launch
-                    self.opt.step(grad_divisor=cnt, seed_base=sb, transposed=tr, loss=(lsum, self.loss_val), keep=kp,
-                                  ranges=rg)
+                # without the regulariser the loss division rides in the optimizer's launch
+                self.opt.step(grad_divisor=cnt, seed_base=sb, transposed=tr, keep=kp, ranges=rg,
+                              loss=None if self.l2 else (lsum, self.loss_val))
                 if self.rshard is not None:
                     self.rshard.zero_foreign()
                     if post:
@@ -786,10 +577,8 @@ class FusedTrainStep:
             else:
                 self._l2(self.loss_out[2:3])
                 sp = self._sparse_spec() if self._sparse_tables is not None else None
-                if self.max_grad_norm is None:
-                    self.opt.step(seed_base=sb, transposed=tr, keep=kp, sparse=sp)
-                else:
-                    self.opt.step(grad_divisor=self._clip_norm(sp), seed_base=sb, transposed=tr, keep=kp, sparse=sp)
+                gd = self._clip_norm(sp) if self.max_grad_norm is not None else None
+                self.opt.step(grad_divisor=gd, seed_base=sb, transposed=tr, keep=kp, sparse=sp)
 
     @staticmethod
     def _check_max_grad_norm(c):
@@ -815,7 +604,7 @@ class FusedTrainStep:
         docstring (max_grad_norm), then the finish launch, on the current stream.  sparse: this step's
         FusedAdam.step `sparse`."""
         f = self.flat
-        segs = [(lo, hi) for lo, hi, _ in self.opt._sparse_segments(sparse)] if sparse else [(0, f.numel)]
+        segs = [(lo, hi) for lo, hi, _ in plan(f.numel, sparse=sparse)]
         sizes = [sum(ops.gradnorm_dense_parts(hi - lo) for lo, hi in segs)] if segs else [0]
         sizes += [ops.gradnorm_rows_parts(d, lst.numel()) for _, _, d, lst, _ in sparse or ()]
         if self._clip_ws is None or self._clip_ws.numel() != sum(sizes):
@@ -847,6 +636,7 @@ class FusedTrainStep:
     EARLY_TOKEN_ADAM_WG = int(os.environ.get("RS_EARLY_TOKEN_ADAM_WG", "256"))
 
     ROW_MARKS_MIN = 16384
+    SGD_STEP_KEY = FusedSGD.SGD_STEP_KEY       # (checkpoints: the device step count's key in an SGD state_dict)
 
     def _early_token_update(self, name):
         """Engine hook (BERTEngine: right after the token table's gradient, before the grouped weight gradients): that
@@ -924,7 +714,7 @@ class FusedTrainStep:
         self.gather_vocab_shards()
         if self.rshard is not None:
             torch.cuda.synchronize()
-            self.rshard.gather_masters([self.flat.data, self.opt.m, self.opt.v])
+            self.rshard.gather_masters([self.flat.data] + self.opt.moment_buffers())
             self.flat.stale = []
 
     def masters_loaded(self):
@@ -947,119 +737,24 @@ class FusedTrainStep:
         return out
 
     def optimizer_state_dict(self):
-        """The optimizer state in torch.optim.Adam's state_dict() layout (param_groups from a real Adam over
-        the same parameters; per-parameter 'step', 'exp_avg', 'exp_avg_sq'), so the reference trainer can
-        resume from it (BS/trainers/base.py:255-259, 'optimizer_state_dict').  With the sharded item table and stale
-        rows (after a step) this is COLLECTIVE: call it on every rank, not from rank 0 alone."""
-        if self.optimizer == "sgd":
-            return self._sgd_state_dict()
+        """The optimizer state in torch.optim.Adam's state_dict() layout (FusedAdam.state_dict; under optimizer="sgd"
+        torch.optim.SGD's, FusedSGD.state_dict), so the reference trainer can resume from it (BS/trainers/base.py:
+        255-259, 'optimizer_state_dict').  With the sharded item table and stale rows (after a step) this is
+        COLLECTIVE: call it on every rank, not from rank 0 alone."""
         if self.rshard is not None and self.flat.stale:
             self.gather_shards()
         torch.cuda.synchronize()
-        hy = self.opt.hyper.cpu().tolist()
-        ref = torch.optim.Adam(self.model.parameters(), lr=hy[0], betas=(hy[1], hy[2]), eps=hy[3], weight_decay=hy[4])
-        sd = ref.state_dict()
-        step = float(self.opt.state[0].item())
-        if step > 0:
-            for i, (p, off) in enumerate(self._param_slices()):
-                n = p.numel()
-                sd["state"][i] = {"step": torch.tensor(step),
-                                  "exp_avg": self.opt.m[off:off + n].view(p.shape).detach().cpu().clone(),
-                                  "exp_avg_sq": self.opt.v[off:off + n].view(p.shape).detach().cpu().clone()}
-        return sd
+        return self.opt.state_dict(list(self.model.parameters()), self._param_slices())
 
     def load_optimizer_state_dict(self, sd):
         """Resume from a torch.optim.Adam state_dict (e.g. a reference checkpoint's 'optimizer_state_dict'); under
         optimizer="sgd", from a torch.optim.SGD one.  The other optimizer's format is a ValueError."""
         g = sd["param_groups"][0]
-        if self.optimizer == "sgd":
-            return self._load_sgd_state_dict(sd)
-        if "betas" not in g:
-            raise ValueError("optimizer='adam' cannot load this optimizer state: its param_groups have no 'betas' (a "
-                             "torch.optim.SGD checkpoint loads into a step built with optimizer='sgd')")
-        if self.table_optim == "sparse" and g["weight_decay"] != 0:
+        if self.table_optim == "sparse" and "betas" in g and g["weight_decay"] != 0:     # (no betas: not Adam's state)
             raise ValueError("table_optim='sparse' needs weight_decay == 0 (the loaded optimizer state has "
                              f"{g['weight_decay']})")
-        self.opt.weight_decay = float(g["weight_decay"])
-        self.opt.hyper.copy_(torch.tensor([g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]],
-                                          dtype=torch.float64))
-        slices = self._param_slices()
-        steps = set()
-        self.opt.m.zero_()
-        self.opt.v.zero_()
-        for i, (p, off) in enumerate(slices):
-            st = sd["state"].get(i)
-            if not st:
-                continue
-            n = p.numel()
-            self.opt.m[off:off + n].copy_(st["exp_avg"].reshape(-1))
-            self.opt.v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
-            steps.add(float(st["step"]))
-        if len(steps) > 1:
-            raise ValueError("per-parameter Adam step counts differ; the fused optimizer keeps one")
-        self.opt.state.zero_()
-        self.opt.state[0] = steps.pop() if steps else 0.0
-
-    # torch.optim.SGD's state_dict carries no step count: the device count (kernel stamps, resumed runs) travels in
-    # this extra param_groups key, which torch.optim.SGD.load_state_dict keeps and never reads
-    SGD_STEP_KEY = "fused_step"
-
-    def _sgd_state_dict(self):
-        """torch.optim.SGD's state_dict() layout: param_groups from a real SGD over the same parameters (torch's own
-        keys) plus SGD_STEP_KEY; state[i] = {'momentum_buffer'} per parameter once a step has run with a non-zero
-        momentum, else empty."""
-        torch.cuda.synchronize()
-        lr, mom, wd = self.opt.hyper.cpu().tolist()
-        sd = torch.optim.SGD(self.model.parameters(), lr=lr, momentum=mom, weight_decay=wd).state_dict()
-        step = float(self.opt.state[0].item())
-        sd["param_groups"][0][self.SGD_STEP_KEY] = step
-        if step > 0 and self.opt.buf is not None:
-            for i, (p, off) in enumerate(self._param_slices()):
-                n = p.numel()
-                sd["state"][i] = {"momentum_buffer": self.opt.buf[off:off + n].view(p.shape).detach().cpu().clone()}
-        return sd
-
-    def _load_sgd_state_dict(self, sd):
-        g = sd["param_groups"][0]
-        if "betas" in g or "momentum" not in g:
-            raise ValueError("optimizer='sgd' cannot load this optimizer state: its param_groups are not "
-                             "torch.optim.SGD's (an Adam checkpoint loads into a step built with optimizer='adam')")
-        if g.get("dampening", 0) != 0:
-            raise ValueError(f"dampening must be 0 (the loaded optimizer state has {g['dampening']}): the fused SGD "
-                             "has none")
-        if g.get("nesterov", False):
-            raise ValueError("nesterov must be False (the loaded optimizer state has nesterov=True): the fused SGD "
-                             "has none")
-        mom = float(g["momentum"])
-        if not math.isfinite(mom) or mom < 0:
-            raise ValueError(f"momentum must be a finite number >= 0 (the loaded optimizer state has {mom})")
-        opt = self.opt
-        if (mom != 0) != (opt.buf is not None) and self.graphs is not None:
-            # a captured graph holds the buffer's pointer and the kernel chosen for its presence: a new or a dropped
-            # buffer would leave the graph on the old one
-            raise ValueError(f"the loaded optimizer state has momentum={mom}, the captured step graphs were built "
-                             f"with momentum={self.momentum}: load it before capture(), or build the step with "
-                             "that momentum")
-        if mom != 0 and opt.buf is None:
-            opt.buf = torch.zeros(self.flat.numel, dtype=torch.float32, device=self.flat.device)
-        elif mom == 0:
-            opt.buf = None
-        opt.momentum = self.momentum = mom
-        opt.weight_decay = float(g["weight_decay"])
-        opt.hyper.copy_(torch.tensor([g["lr"], mom, g["weight_decay"]], dtype=torch.float64))
-        seen = 0
-        if opt.buf is not None:
-            opt.buf.zero_()
-            for i, (p, off) in enumerate(self._param_slices()):
-                st = sd["state"].get(i)
-                b = st.get("momentum_buffer") if st else None
-                if b is None:       # torch: no buffer yet -> its first step clones the gradient, as a zero one does
-                    continue
-                opt.buf[off:off + p.numel()].copy_(b.reshape(-1))
-                seen += 1
-        opt.state.zero_()
-        # a checkpoint torch.optim.SGD wrote has no count: 1 when it holds buffers (some step ran), else 0
-        opt.state[0] = float(g.get(self.SGD_STEP_KEY, 1.0 if seen else 0.0))
+        self.opt.load_state_dict(sd, self._param_slices(), captured=self.graphs is not None)
+        self.momentum = self.opt.momentum
 
     def gather_vocab_shards(self):
         """Vocabulary-sharded step: make this rank's out.weight / out.bias (and their Adam moments) hold every
@@ -1068,7 +763,7 @@ class FusedTrainStep:
             return
         torch.cuda.synchronize()
         for name in ("out.weight", "out.bias"):
-            for buf in (self.flat.data, self.opt.m, self.opt.v):
+            for buf in [self.flat.data] + self.opt.moment_buffers():
                 self.vshard.gather_rows(self.flat.view(name, buf))
         self.engine.sync_compute_weights()
 
@@ -1261,7 +956,6 @@ class FusedTrainStep:
                     self.graph_collectives = False
                     if self.steps_per_graph > 1:   # every rank raises alike; the caller re-captures with S = 1
                         raise RuntimeError(f"all-reduce capture failed on some rank ({err or 'not this one'})")
-                    import warnings
                     warnings.warn(f"all-reduce capture failed on some rank ({err or 'not this one'}); falling back "
                                   f"to segmented DP graphs on every rank")
                     return self._capture_graphs_impl(compute, stamps, unrolled)

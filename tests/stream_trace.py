@@ -11,7 +11,8 @@ and every ``torch.cuda.Event.record`` / ``torch.cuda.Stream.wait_event`` / ``tor
 Streams are labelled s0, s1, ... and events numbered 0, 1, ... in order of first appearance within one trace; a
 stream's identity is its handle, an event's the object.  ``wait_stream`` is one entry (torch forms it from an event of
 its own, which is not listed).  Only torch's own primitives and ``ops.call`` are patched, so the recorder runs on any
-revision of the package; tests/golden/step_traces.json holds the traces of the revision before the side-branch helper.
+revision of the package; tests/golden/step_traces.json holds the traces of the revision before the side-branch helper
+(the optimizer variants at the end of CASES: of the revision before the optimizers moved into rbm_amd.optim).
 """
 import argparse
 
@@ -80,7 +81,7 @@ def streams(trace):
 
 
 # ------------------------------------------------------------------ the cases
-def _sas(d, dtype, loss, turnaround="1", K=0):
+def _sas(d, dtype, loss, turnaround="1", K=0, **step_kw):
     def make(monkeypatch):
         import rbm_amd.data as synth
         from rbm_amd.models import model_factory
@@ -91,7 +92,7 @@ def _sas(d, dtype, loss, turnaround="1", K=0):
         a = argparse.Namespace(model_code="sas", num_items=V, max_len=T, device="cuda", sas_hidden_units=d,
                                sas_num_blocks=2, sas_heads=1, sas_dropout=0.2, l2_emb=0.0, rs_dtype=dtype,
                                sas_loss=loss, sas_shared_negs=K)
-        tr = FusedTrainStep(model_factory(a), lr=1e-3)
+        tr = FusedTrainStep(model_factory(a), lr=1e-3, **step_kw)
         rng = np.random.default_rng(7)
         batches = []
         for _ in range(2):
@@ -103,7 +104,7 @@ def _sas(d, dtype, loss, turnaround="1", K=0):
     return make
 
 
-def _bert(V, T, d, L, h, B, loss=None, K=0):
+def _bert(V, T, d, L, h, B, loss=None, K=0, **step_kw):
     def make(monkeypatch):
         import rbm_amd.data as synth
         from rbm_amd.models import model_factory
@@ -114,7 +115,7 @@ def _bert(V, T, d, L, h, B, loss=None, K=0):
                                bert_mask_prob=0.2, model_init_seed=0, rs_dtype="bf16")
         m = model_factory(a)
         m.train()
-        tr = FusedTrainStep(m, lr=1e-3, loss=loss)
+        tr = FusedTrainStep(m, lr=1e-3, loss=loss, **step_kw)
         rng = np.random.default_rng(7)
         batches = []
         for _ in range(2):
@@ -138,6 +139,12 @@ CASES = {
     "bert_ce": _bert(300, 24, 64, 1, 2, 8),
     "bert_sampled_ce": _bert(300, 24, 64, 1, 2, 8, loss="sampled_ce", K=50),
     "bert_big_vocab": _bert(BIG_V, 8, 64, 1, 2, 2),
+    # the optimizer variants (recorded at the revision before the optimizers moved into rbm_amd.optim)
+    "sas_bce_sgd_momentum": _sas(64, "bf16", "bce", optimizer="sgd", momentum=0.9),
+    "sas_bce_sparse_tables": _sas(64, "bf16", "bce", table_optim="sparse"),
+    "sas_bce_clip": _sas(64, "bf16", "bce", max_grad_norm=1.0),
+    "bert_sampled_ce_sparse_clip": _bert(300, 24, 64, 1, 2, 8, loss="sampled_ce", K=50, table_optim="sparse",
+                                         max_grad_norm=1.0),
 }
 
 
