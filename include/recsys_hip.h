@@ -1058,6 +1058,54 @@ int rs_sce_head_logq_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int6
 int rs_alias_items(const uint64_t* seed_base, uint64_t salt, const uint64_t* table, int64_t item_num, int64_t K,
                    int64_t* out, void* stream);
 
+/* ---- on-device evaluation loader: seeded per-user negatives and evaluation batches (eval_loader.hip) ----
+ * Replaces the reference's test negatives (BS/dataloaders/negative_samplers/random.py:18-35, popular.py:25-42) and its
+ * evaluation datasets (SASEvalDataset, BS/dataloaders/sas.py:125-153; BertEvalDataset, BS/dataloaders/bert.py:116-142).
+ *
+ * rs_eval_negatives: for the users u in [user0, user0 + count) it writes negs[u * n_neg + 0 .. n_neg) (int32; negs,
+ * n_drawn and draws are indexed by the ABSOLUTE user u, as seen_offsets is).  User u owns a raw draw stream
+ *   k(u)    = splitmix64(seed ^ (A * (u + 1)))                    A = 0xA0761D6478BD642F, 64-bit wrap-around
+ *   r(u, c) = splitmix64(k(u) + C * (c + 1)),  c = 0, 1, ...       C = 0x632BE59BD9B4E019 (rs_uniform_items' constant)
+ *   s       = umulhi(r, item_num)                                  the high 64 bits of r * item_num, < item_num
+ *   x(u, c) = s + 1                                                table == NULL: uniform over [1, item_num]
+ *   x(u, c) = frac < thr[s] ? s + 1 : alias[s],  frac = (uint32)((r * item_num mod 2^64) >> 32)
+ *                                                                  table: a packed alias table, exactly rs_alias_items' rule
+ * with splitmix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB; return z ^ z >> 31.  negs[u] is that stream with every item of seen(u) dropped and every repeat
+ * of an earlier kept item dropped, the first n_neg survivors in stream order (RandomNegativeSampler's `while item in
+ * seen or item in samples` loop on the stream).  seen(u) = seen_sorted[seen_offsets[u] .. seen_offsets[u + 1]) (int32,
+ * ascending, unique): the user's WHOLE history, train + val + test.  x depends on (seed, u, c) only: one call over all
+ * users equals any split into several calls.
+ * Bounds: 1 <= n_neg <= rs_eval_negs_max() (1024), n_neg <= item_num < 2^31.  At most rs_eval_negatives_max_draws()
+ * (4096; host only) raw draws are read per user; the slots still open then take the smallest ids of [1, item_num] that
+ * are neither seen nor kept, ascending.  The caller guarantees item_num - |seen(u)| >= n_neg (slots that cannot be
+ * filled get 0).  n_drawn (nullable, int32 [users]): the raw draws consumed, c + 1 of the draw that filled the last
+ * slot, or -1 - (slots filled by the fallback).
+ * rs_eval_negatives_draws: the same negs, and draws[u * max_draws + c] = x(u, c) (int64) for every c < max_draws,
+ * before any filtering (tests replay the reference's loop on them).
+ *
+ * rs_eval_batch: for the users u = user0 + b, b in [0, B), one row each of
+ *   seq    int64 [B][max_len]: the last max_len of  history(u) (+ extra[u] when extra != NULL: the validation item of
+ *          test mode) (+ mask_token when mask_token > 0: BERT appends [MASK] BEFORE truncating), left padded with 0;
+ *          history(u) = hist_items[hist_offsets[u] .. hist_offsets[u + 1]) (int64, may be empty)
+ *   cand   int64 [B][1 + n_neg] = {answer[u], negs[u * n_neg + 0 .. n_neg)}
+ *   labels int64 [B][1 + n_neg] = {1, 0, ..., 0}
+ * extra / answer: int64 [users]; negs as rs_eval_negatives writes it.  1 <= max_len <= 512, n_neg as above.
+ *
+ * Every refusal is made on the host before any launch: RS_ERR_ARG for a NULL pointer (table, n_drawn, extra are
+ * optional), user0 < 0, a non-positive size, or n_neg / item_num / max_len out of range.  No allocation, no sync. */
+int64_t rs_eval_negs_max(void);
+int64_t rs_eval_negatives_max_draws(void);
+int rs_eval_negatives(const int64_t* seen_offsets, const int32_t* seen_sorted, int64_t user0, int64_t count,
+                      int64_t item_num, int64_t n_neg, uint64_t seed, const uint64_t* table, int32_t* negs,
+                      int32_t* n_drawn, void* stream);
+int rs_eval_negatives_draws(const int64_t* seen_offsets, const int32_t* seen_sorted, int64_t user0, int64_t count,
+                            int64_t item_num, int64_t n_neg, uint64_t seed, const uint64_t* table, int32_t* negs,
+                            int32_t* n_drawn, int64_t* draws, void* stream);
+int rs_eval_batch(const int64_t* hist_offsets, const int64_t* hist_items, const int64_t* extra, const int64_t* answer,
+                  const int32_t* negs, int64_t user0, int64_t B, int64_t max_len, int64_t n_neg, int64_t mask_token,
+                  int64_t* seq, int64_t* cand, int64_t* labels, void* stream);
+
 /* ABI version of this header/library pair. */
 int rs_abi_version(void);
 /* sizeof of the structs of this header that bindings mirror (host only); -1 for an unknown index. */

@@ -229,6 +229,11 @@ SIGNATURES = {
     "rs_sce_head_logq_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                              vp, vp],
     "rs_alias_items": [vp, u64, vp, i64, i64, vp, vp],
+    "rs_eval_negs_max": [],
+    "rs_eval_negatives_max_draws": [],
+    "rs_eval_negatives": [vp, vp, i64, i64, i64, i64, u64, vp, vp, vp, vp],
+    "rs_eval_negatives_draws": [vp, vp, i64, i64, i64, i64, u64, vp, vp, vp, vp, vp],
+    "rs_eval_batch": [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp],
     "rs_kernel_stamps": [vp, vp, i32],
     "rs_kernel_stamp_count": [],
     "rs_kernel_stamp_kinds": [C.POINTER(i32), i32],
@@ -247,7 +252,8 @@ RESTYPES = {"rs_wgrad_grouped_slab_numel": C.c_int64, "rs_abi_sizeof": C.c_int64
             "rs_sas_block_grid": C.c_int64, "rs_layernorm_bwd_nparts": C.c_int64,
             "rs_sas_ce_rows_nparts": C.c_int64, "rs_sas_sce_max_k": C.c_int64,
             "rs_sas_sce_ws_bytes": C.c_int64, "rs_sas_sce_dh_splits": C.c_int64,
-            "rs_sce_head_ws_bytes": C.c_int64, "rs_sce_head_dh_splits": C.c_int64}
+            "rs_sce_head_ws_bytes": C.c_int64, "rs_sce_head_dh_splits": C.c_int64,
+            "rs_eval_negs_max": C.c_int64, "rs_eval_negatives_max_draws": C.c_int64}
 
 _lib = None
 

@@ -21,6 +21,11 @@ ItemProposal: a non-uniform proposal over the items for the shared candidates of
 sampling, the reference's ``negative_samplers/popular.py`` moved into the loss): a fixed-point alias table the
 device draws from (rs_alias_items) and the log of the distribution those draws realise, which the loss subtracts
 from every logit (the logQ correction; ``sampled_ce_loss(..., logq=)``).
+
+DeviceEvalNegatives / DeviceEvalLoader: the evaluation side -- the reference's per-user test negatives
+(BS/dataloaders/negative_samplers) drawn once on the device by rs_eval_negatives, and the validation / test batches of
+SASEvalDataset / BertEvalDataset (BS/dataloaders/sas.py:125-153, bert.py:116-142) built on the device by rs_eval_batch.
+``rbm_amd.metrics.evaluate`` runs a model over such a loader.
 """
 import math
 
@@ -136,6 +141,183 @@ def _check_proposal(proposal, shared_negs, item_num, device):
     pd = proposal.table.device
     if pd.type != device.type or (device.index is not None and pd.index != device.index):
         raise ValueError(f"the proposal lives on {proposal.table.device}, the sampler on {device}")
+
+
+def _per_user(x, what):
+    """list of per-user entries from a list or the reference's dict keyed 0 .. n - 1"""
+    if isinstance(x, dict):
+        if sorted(x) != list(range(len(x))):
+            raise ValueError(f"{what}: a dict must be keyed by the users 0 .. n - 1")
+        return [x[u] for u in range(len(x))]
+    return list(x)
+
+
+def _one_answer(x, what):
+    """(n_users,) int64 of a split that holds exactly one item per user (leave-one-out): [item] or a bare id"""
+    out = np.empty(len(x), np.int64)
+    for u, a in enumerate(x):
+        if isinstance(a, (int, np.integer)):
+            out[u] = a
+        elif hasattr(a, "__len__") and len(a) == 1:
+            out[u] = a[0]
+        else:
+            raise ValueError(f"{what}[{u}] must hold exactly one item (leave-one-out), got {a!r}")
+    return out
+
+
+def _csr(histories):
+    lens = np.fromiter((len(s) for s in histories), dtype=np.int64, count=len(histories))
+    off = np.zeros(len(histories) + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    flat = np.fromiter((i for s in histories for i in s), dtype=np.int64, count=int(off[-1]))
+    return off, flat
+
+
+def _eval_splits(train, val, test, item_num):
+    train, val, test = _per_user(train, "train"), _per_user(val, "val"), _per_user(test, "test")
+    if not train or not (len(train) == len(val) == len(test)):
+        raise ValueError("train, val and test must hold the same, non-zero number of users")
+    off, flat = _csr(train)
+    v, t = _one_answer(val, "val"), _one_answer(test, "test")
+    for a in (flat, v, t):
+        if a.size and (a.min() < 1 or a.max() > item_num):
+            raise ValueError("an item id lies outside [1, item_num]")
+    if flat.size == 0:
+        raise ValueError("the training histories are all empty")
+    return off, flat, v, t
+
+
+class DeviceEvalNegatives:
+    """The reference's ``test_negative_samples`` (BS/dataloaders/negative_samplers): per user n_neg distinct items
+    the user never interacted with (train + val + test), generated once on the device by rs_eval_negatives and shared
+    by the validation and the test loader.
+
+    sampler="random": RandomNegativeSampler's rejection loop on a seeded per-user uniform stream.  sampler="popular":
+    the stream is drawn from ``ItemProposal.from_histories(train + val + test, item_num, alpha=1, smooth=0)`` (or from
+    ``proposal``), which has the law of PopularNegativeSampler's ``np.random.choice(replace=False, p)`` (successive
+    sampling = an i.i.d. stream with repeats dropped), not numpy's stream.  An item that never occurs has weight 0 and
+    ItemProposal refuses it (ValueError): pass ``proposal=ItemProposal.from_histories(..., smooth=1)`` to give such
+    items a positive weight.
+
+    .negs: int32 (n_users, n_neg) on the device.  .n_drawn: int32 (n_users,), the raw draws each user consumed, or
+    -1 - k for a user whose last k slots were filled by the bounded fallback (rs_eval_negatives).  .fallback_users: how
+    many users that is (one host read)."""
+
+    def __init__(self, train, val, test, item_num, n_neg=100, sampler="random", seed=None, device="cuda",
+                 proposal=None):
+        if sampler not in ("random", "popular"):
+            raise ValueError(f"sampler must be 'random' or 'popular', got {sampler!r}")
+        self.item_num, self.n_neg, self.sampler = int(item_num), int(n_neg), sampler
+        if not 1 <= self.item_num < 2 ** 31:
+            raise ValueError("item_num must be in [1, 2^31)")
+        if not 1 <= self.n_neg <= ops.eval_negs_max():
+            raise ValueError(f"n_neg must be in 1..{ops.eval_negs_max()}, got {n_neg}")
+        off, flat, v, t = _eval_splits(train, val, test, self.item_num)
+        self.n_users = n = len(off) - 1
+        # seen(u): the whole history, sorted and unique per user (one sort of user * (V + 1) + item)
+        users = np.concatenate([np.repeat(np.arange(n, dtype=np.int64), np.diff(off)), np.arange(n), np.arange(n)])
+        key = np.unique(users * (self.item_num + 1) + np.concatenate([flat, v, t]))
+        n_seen = np.bincount(key // (self.item_num + 1), minlength=n)
+        short = np.nonzero(self.item_num - n_seen < self.n_neg)[0]
+        if short.size:
+            raise ValueError(f"user {int(short[0])} has {int(n_seen[short[0]])} seen items of {self.item_num}: fewer "
+                             f"than n_neg = {self.n_neg} are left (the reference's sampler would loop forever)")
+        if sampler == "popular" and proposal is None:
+            proposal = ItemProposal.from_histories([flat, v, t], self.item_num, alpha=1.0, smooth=0.0, device=device)
+        if sampler == "random":
+            proposal = None
+        elif proposal.item_num != self.item_num:
+            raise ValueError(f"proposal.item_num = {proposal.item_num}, item_num = {self.item_num}")
+        self.proposal = proposal
+        self.device = torch.device(device)
+        g = torch.Generator().manual_seed(seed) if seed is not None else None
+        self.seed = int(torch.randint(0, 2 ** 62, (1,), generator=g).item())
+        seen_off = np.zeros(n + 1, np.int64)
+        np.cumsum(n_seen, out=seen_off[1:])
+        self.seen_offsets = torch.from_numpy(seen_off).to(self.device)
+        self.seen_sorted = torch.from_numpy((key % (self.item_num + 1)).astype(np.int32)).to(self.device)
+        self.negs = torch.empty((n, self.n_neg), dtype=torch.int32, device=self.device)
+        self.n_drawn = torch.empty(n, dtype=torch.int32, device=self.device)
+        ops.eval_negatives(self.seen_offsets, self.seen_sorted, self.item_num, self.seed, self.negs,
+                           table=None if proposal is None else proposal.table, n_drawn=self.n_drawn)
+        self.fallback_users = int((self.n_drawn < 0).sum().item())
+
+    @classmethod
+    def from_samples(cls, samples, device="cuda"):
+        """Adopt negatives generated elsewhere -- the dict {user: [items]} the reference pickles, or an (n_users,
+        n_neg) array -- so that two runs can be compared on identical candidates."""
+        if isinstance(samples, dict):
+            samples = _per_user(samples, "samples")
+        a = np.asarray(samples)
+        if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("samples must be n_users rows of the same number (>= 1) of integer item ids")
+        if a.shape[1] > ops.eval_negs_max():
+            raise ValueError(f"n_neg must be in 1..{ops.eval_negs_max()}, got {a.shape[1]}")
+        if a.min() < 1 or a.max() >= 2 ** 31:
+            raise ValueError("an item id lies outside [1, 2^31)")
+        self = cls.__new__(cls)
+        self.n_users, self.n_neg = a.shape
+        self.item_num, self.sampler, self.seed, self.proposal = None, "samples", None, None
+        self.device = torch.device(device)
+        self.negs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        self.n_drawn, self.fallback_users = None, 0
+        return self
+
+
+class DeviceEvalLoader:
+    """The reference's validation / test loader (``_get_eval_loader``: SASEvalDataset / BertEvalDataset behind a
+    ``DataLoader(shuffle=False)``) with every batch built on the device by rs_eval_batch.
+
+    Iterates the users in order in ceil(n_users / batch_size) batches (the last one partial) of (seq, candidates,
+    labels), int64 device tensors of shapes (b, max_len), (b, 1 + n_neg), (b, 1 + n_neg): seq = the last max_len of
+    train (mode="val") or train + the validation item (mode="test"), for model_code="bert" with [MASK] = item_num + 1
+    appended before the truncation, left padded with 0; candidates = the answer (val / test item) then the user's
+    negatives; labels = 1 then zeros.  val and test hold exactly one item per user ([item] or the bare id)."""
+
+    def __init__(self, train, val, test, item_num, batch_size, max_len, negatives, mode="val", model_code="sas",
+                 device="cuda"):
+        if mode not in ("val", "test"):
+            raise ValueError(f"mode must be 'val' or 'test', got {mode!r}")
+        if model_code not in ("sas", "bert"):
+            raise ValueError(f"model_code must be 'sas' or 'bert', got {model_code!r}")
+        self.item_num, self.batch_size, self.max_len = int(item_num), int(batch_size), int(max_len)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        if not 1 <= self.max_len <= 512:
+            raise ValueError("max_len must be in 1..512")
+        off, flat, v, t = _eval_splits(train, val, test, self.item_num)
+        self.n_users = len(off) - 1
+        if negatives.n_users != self.n_users:
+            raise ValueError(f"negatives hold {negatives.n_users} users, the splits {self.n_users}")
+        self.device = torch.device(device)
+        if negatives.negs.device != self.device and not (
+                self.device.index is None and negatives.negs.device.type == self.device.type):
+            raise ValueError(f"the negatives live on {negatives.negs.device}, the loader on {self.device}")
+        self.mode, self.model_code, self.negatives = mode, model_code, negatives
+        self.mask_token = self.item_num + 1 if model_code == "bert" else 0
+        self.offsets = torch.from_numpy(off).to(self.device)
+        self.items = torch.from_numpy(flat).to(self.device)
+        self.extra = torch.from_numpy(v).to(self.device) if mode == "test" else None
+        self.answer = torch.from_numpy(t if mode == "test" else v).to(self.device)
+
+    def batch(self, i):
+        """batch i of len(self): (seq, candidates, labels)"""
+        u0 = i * self.batch_size
+        b = min(self.batch_size, self.n_users - u0)
+        if i < 0 or b < 1:
+            raise IndexError(i)
+        C = 1 + self.negatives.n_neg
+        seq = torch.empty((b, self.max_len), dtype=torch.int64, device=self.device)
+        cand, labels = (torch.empty((b, C), dtype=torch.int64, device=self.device) for _ in range(2))
+        ops.eval_batch(self.offsets, self.items, self.extra, self.answer, self.negatives.negs, u0, self.mask_token,
+                       seq, cand, labels)
+        return seq, cand, labels
+
+    def __iter__(self):
+        return (self.batch(i) for i in range(len(self)))
+
+    def __len__(self):
+        return -(-self.n_users // self.batch_size)
 
 
 class DeviceWarpSampler:

@@ -1225,6 +1225,53 @@ def rank_metrics(scores, labels, ks_dev, ws, out):
     call("rs_rank_metrics", ptr(scores), ptr(labels), R, C, ks_dev.numel(), ptr(ks_dev), ptr(ws), ptr(out), stream())
 
 
+# ---- evaluation loader: per-user negatives and eval batches (eval_loader.hip) ----------------
+def eval_negs_max():
+    return int(_lib.lib().rs_eval_negs_max())
+
+
+def eval_negatives_max_draws():
+    return int(_lib.lib().rs_eval_negatives_max_draws())
+
+
+def eval_negatives(seen_offsets, seen_sorted, item_num, seed, negs, table=None, n_drawn=None, draws=None, user0=0,
+                   count=None):
+    """negs (int32 (n_users, n_neg), device) rows [user0, user0 + count) <- the seeded per-user negatives of
+    rs_eval_negatives: seen_offsets int64 (n_users + 1,), seen_sorted int32 (each user's whole history, ascending,
+    unique), table None (uniform) or ItemProposal.table, n_drawn int32 (n_users,) optional, draws (tests) int64
+    (n_users, eval_negatives_max_draws()) record of the raw stream (rs_eval_negatives_draws)."""
+    n_users, n_neg = negs.shape
+    count = n_users - user0 if count is None else count
+    assert seen_offsets.dtype == torch.int64 and seen_offsets.numel() == n_users + 1 and seen_offsets.is_contiguous()
+    assert seen_sorted.dtype == torch.int32 and seen_sorted.is_contiguous()
+    assert negs.dtype == torch.int32 and negs.is_contiguous() and 0 <= user0 and user0 + count <= n_users
+    assert n_drawn is None or (n_drawn.dtype == torch.int32 and n_drawn.numel() == n_users and n_drawn.is_contiguous())
+    assert table is None or (table.dtype == torch.int64 and table.numel() == item_num and table.is_contiguous())
+    seed = int(seed) & (2 ** 64 - 1)
+    if draws is not None:
+        assert draws.dtype == torch.int64 and draws.is_contiguous()
+        assert draws.shape == (n_users, eval_negatives_max_draws())
+        call("rs_eval_negatives_draws", ptr(seen_offsets), ptr(seen_sorted), user0, count, item_num, n_neg, seed,
+             ptr(table), ptr(negs), ptr(n_drawn), ptr(draws), stream())
+        return
+    call("rs_eval_negatives", ptr(seen_offsets), ptr(seen_sorted), user0, count, item_num, n_neg, seed, ptr(table),
+         ptr(negs), ptr(n_drawn), stream())
+
+
+def eval_batch(hist_offsets, hist_items, extra, answer, negs, user0, mask_token, seq, cand, labels):
+    """rs_eval_batch: the rows of the users [user0, user0 + B) into seq (B, T), cand and labels (B, 1 + n_neg), int64
+    device tensors.  extra None (validation) or the per-user validation item (test); mask_token 0 (SAS) or [MASK]."""
+    n_users, n_neg = negs.shape
+    B, T = seq.shape
+    assert hist_offsets.dtype == torch.int64 and hist_offsets.numel() == n_users + 1 and hist_items.dtype == torch.int64
+    assert answer.dtype == torch.int64 and answer.numel() == n_users and negs.dtype == torch.int32
+    assert extra is None or (extra.dtype == torch.int64 and extra.numel() == n_users)
+    assert 0 <= user0 and user0 + B <= n_users and cand.shape == (B, 1 + n_neg) and labels.shape == (B, 1 + n_neg)
+    assert all(t.dtype == torch.int64 and t.is_contiguous() for t in (seq, cand, labels)) and negs.is_contiguous()
+    call("rs_eval_batch", ptr(hist_offsets), ptr(hist_items), ptr(extra), ptr(answer), ptr(negs), user0, B, T, n_neg,
+         mask_token, ptr(seq), ptr(cand), ptr(labels), stream())
+
+
 # ---- full-catalogue ranking and top-K (fullrank.hip) ----------------------------------------
 RS_TOPK_MAX = 128
 
