@@ -350,6 +350,13 @@ int rs_vocab_head_fwd(int64_t R, int64_t V1, int64_t d, const void* h, int64_t l
 int rs_vocab_head_bwd(int64_t R, int64_t V1, int64_t d, const void* h, int64_t ldh, const void* E, int64_t lde,
                       const float* bias, const int64_t* labels, const int* rows_dev, const float* count,
                       const float* dloss, const float* ws, void* dlogits, int64_t lddl, int64_t voff, void* stream);
+/* Host-only (no launch, no allocation): the form rs_vocab_head_fwd (bwd = 0) / rs_vocab_head_bwd (bwd = 1) take for
+ * R rows, V1 classes and width d on a device of `cus` compute units (cus <= 0: the current device's), from the
+ * host functions the launchers themselves call; RS_VHEAD_PP is honoured.  out[0] = 1: the ping-pong kernels, 0: the
+ * lock-step kernels (RS_VHEAD_PP=0, or a backward whose per-row metadata, 8 bytes per row of a workgroup's row
+ * range, does not fit LDS); out[1], out[2] = gridDim.x, gridDim.y; out[3] = row tiles (32 rows ping-pong, 128 rows
+ * lock-step) per y-group; out[4] = dynamic LDS bytes. */
+int rs_vocab_head_form(int bwd, int64_t R, int64_t V1, int64_t d, int cus, int* out);
 
 /* Vocabulary-sharded head (data-parallel rank r owns rows [v0, v1) of E = out.weight and b;
  * every rank holds the labelled rows h of ALL ranks, all-gathered).  Labels stay absolute vocabulary ids

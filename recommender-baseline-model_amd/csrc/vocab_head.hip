@@ -297,7 +297,6 @@ __global__ __launch_bounds__(NTH, 1) void vhead_kernel(Args a) {
           const int64_t lb = labs[rl];
           const bool live = m0 + rl < Rl && lb != 0;
           const float Lr = lses[rl];
-          const float scr = live ? sc : 0.f;
           const int64_t offl = lb - a.voff - (n0 + v0w + 4 * g);   // label's entry in this lane's rows
           const int off = offl < 0 || offl >= 64 ? -1 : (int)offl;
 #pragma unroll
@@ -306,7 +305,9 @@ __global__ __launch_bounds__(NTH, 1) void vhead_kernel(Args a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const float x = acc[i][j][r] + bia[i][r];
-              float gv = (__expf(x - Lr) - (off == 16 * i + r ? 1.f : 0.f)) * scr;
+              // dead rows (label 0; their stored lse is 0) by a select: exp(x - 0) overflows past x = 88.7 and
+              // inf * 0 would be NaN
+              float gv = live ? (__expf(x - Lr) - (off == 16 * i + r ? 1.f : 0.f)) * sc : 0.f;
               if (ragged) gv = 16 * i + r < lim ? gv : 0.f;
               o[r] = (bf16)gv;
             }
@@ -342,6 +343,26 @@ __global__ __launch_bounds__(NTH, 1) void vhead_kernel(Args a) {
   }
 }
 
+inline int device_cus() {
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus;
+}
+
+// what a launch of either form looks like (rs_vocab_head_form reports it): grid, row tiles per y-group, dynamic LDS
+struct Geom {
+  int64_t gx, gy, tiles, lds;
+};
+
+// fewer vocabulary tiles than CUs (cfg3: 105 / 209 of 256): split the row tiles over gridDim.y groups so that
+// up to one workgroup per CU runs (the 1M-vocabulary shapes keep one group, persistent over vocabulary tiles)
+template <int DK, int BV, bool BWD>
+Geom geom(int64_t R, int64_t V1, int cus) {
+  const int64_t nvt = cdiv(V1, BV), nmt = cdiv(R, BR);
+  const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(nmt, (int64_t)cus / nvt));
+  return {std::min<int64_t>(nvt, (int64_t)cus), gy, cdiv(nmt, gy), (int64_t)L<DK, BV, BWD>::LDS};
+}
+
 template <int DK, int BV, bool BWD>
 hipError_t launch(Args& a, hipStream_t s) {
   using C = L<DK, BV, BWD>;
@@ -352,14 +373,9 @@ hipError_t launch(Args& a, hipStream_t s) {
                               C::LDS);
     attr = true;
   }
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int64_t nvt = cdiv(a.V1, BV);
-  const int64_t grid = std::min<int64_t>(nvt, (int64_t)cus);
-  // fewer vocabulary tiles than CUs (cfg3: 105 / 209 of 256): split the row tiles over gridDim.y groups so that
-  // up to one workgroup per CU runs (the 1M-vocabulary shapes keep one group, persistent over vocabulary tiles)
-  const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(cdiv(a.R, BR), (int64_t)cus / nvt));
-  hipLaunchKernelGGL((vhead_kernel<DK, BV, BWD>), dim3((unsigned)grid, (unsigned)gy), dim3(NTH), C::LDS, s, a);
+  const Geom g = geom<DK, BV, BWD>(a.R, a.V1, device_cus());
+  hipLaunchKernelGGL((vhead_kernel<DK, BV, BWD>), dim3((unsigned)g.gx, (unsigned)g.gy), dim3(NTH), (unsigned)g.lds, s,
+                     a);
   return hipGetLastError();
 }
 
@@ -708,25 +724,33 @@ __global__ __launch_bounds__(NTH, 1) void pp_kernel(Args a) {
   }
 }
 
+// the ping-pong launch's geometry; fits = false when the backward's per-row metadata (8 B per row of the workgroup's
+// range) would not fit LDS beside C::FIXED
+template <int DK, bool BWD>
+Geom geom_pp(int64_t R, int64_t V1, int cus, bool* fits) {
+  using P = C<DK, BWD>;
+  const int64_t nvt = cdiv(V1, BV), nmt = cdiv(R, BRT);
+  const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(nmt, (int64_t)cus / nvt));
+  const int64_t tiles = cdiv(nmt, gy);
+  const int64_t lds = P::FIXED + (BWD ? 8 * BRT * tiles : 0);
+  *fits = lds <= LDS_MAX;
+  return {std::min<int64_t>(nvt, (int64_t)cus), gy, tiles, lds};
+}
+
 // returns hipErrorNotSupported when the backward's per-row metadata would not fit LDS (the caller falls back)
 template <int DK, bool BWD>
 hipError_t launch_pp(Args& a, hipStream_t s) {
   using P = C<DK, BWD>;
   static_assert(P::FIXED <= LDS_MAX, "LDS budget");
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int64_t nvt = cdiv(a.V1, BV);
-  const int64_t grid = std::min<int64_t>(nvt, (int64_t)cus);
-  const int64_t nmt = cdiv(a.R, BRT);
-  const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(nmt, (int64_t)cus / nvt));
-  const int64_t lds = P::FIXED + (BWD ? 8 * BRT * cdiv(nmt, gy) : 0);
-  if (lds > LDS_MAX) return hipErrorNotSupported;
+  bool fits = false;
+  const Geom g = geom_pp<DK, BWD>(a.R, a.V1, device_cus(), &fits);
+  if (!fits) return hipErrorNotSupported;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)pp_kernel<DK, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     attr = true;
   }
-  hipLaunchKernelGGL((pp_kernel<DK, BWD>), dim3((unsigned)grid, (unsigned)gy), dim3(NTH), (unsigned)lds, s, a);
+  hipLaunchKernelGGL((pp_kernel<DK, BWD>), dim3((unsigned)g.gx, (unsigned)g.gy), dim3(NTH), (unsigned)g.lds, s, a);
   return hipGetLastError();
 }
 }  // namespace pp
@@ -754,6 +778,17 @@ hipError_t dispatch(Args& a, int64_t d, hipStream_t s) {
   return launch<64, BV, BWD>(a, s);
 }
 
+// the form and geometry dispatch<BWD> gives these sizes on a device of `cus` CUs, from the launchers' own helpers
+template <int DK, bool BWD>
+void form_of(int64_t R, int64_t V1, int cus, int* out) {
+  bool pp_form = false;
+  Geom g{};
+  if (use_pp()) g = pp::geom_pp<DK, BWD>(R, V1, cus, &pp_form);
+  if (!pp_form) g = geom<DK, BWD ? 128 : 256, BWD>(R, V1, cus);
+  out[0] = pp_form ? 1 : 0;
+  out[1] = (int)g.gx; out[2] = (int)g.gy; out[3] = (int)g.tiles; out[4] = (int)g.lds;
+}
+
 }  // namespace vh
 
 // partials -> lse / loss (vocab_ce.hip); with h != null the label logits are formed there (<h, E[label]> + b)
@@ -765,6 +800,15 @@ hipError_t vce_finish(const float* part, int64_t ntn, int64_t R, const int64_t* 
 extern "C" {
 
 int rs_vocab_head_supported(int64_t d) { return d == 64 || d == 128 || d == 256; }
+
+int rs_vocab_head_form(int bwd, int64_t R, int64_t V1, int64_t d, int cus, int* out) {
+  if (!rs_vocab_head_supported(d) || R <= 0 || V1 <= 0 || (bwd != 0 && bwd != 1) || !out) return RS_ERR_ARG;
+  if (cus <= 0) cus = vh::device_cus();
+  if (d == 256) bwd ? vh::form_of<256, true>(R, V1, cus, out) : vh::form_of<256, false>(R, V1, cus, out);
+  else if (d == 128) bwd ? vh::form_of<128, true>(R, V1, cus, out) : vh::form_of<128, false>(R, V1, cus, out);
+  else bwd ? vh::form_of<64, true>(R, V1, cus, out) : vh::form_of<64, false>(R, V1, cus, out);
+  return 0;
+}
 
 int rs_vocab_head_fwd(int64_t R, int64_t V1, int64_t d, const void* h, int64_t ldh, const void* E, int64_t lde,
                       const float* bias, const int64_t* labels, const int* rows_dev, const float* count_override,

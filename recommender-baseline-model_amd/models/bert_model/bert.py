@@ -45,6 +45,12 @@ BERT_LOSSES = ("ce", "sampled_ce")
 SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
 
 
+def head_dh_splits(V1):
+    """Split-K factor of dh = dlogits E over V1 classes (rs_gemm + a slab reduce): one split per 2,048 classes, at
+    most 64."""
+    return int(max(1, min(64, -(-V1 // 2048))))
+
+
 def _check_shared_negs(K):
     kmax = ops.sas_sce_max_k()
     if K < 1 or K > kmax:
@@ -649,7 +655,7 @@ class BERTEngine:
             ops.gemm_n256(dl, self.W("out.weight"), slab_d.view(sk, cap, d), False, cap, self.V1, split=True,
                           rows_dev=cnt)
         else:
-            sk = int(max(1, min(64, -(-self.V1 // 2048))))
+            sk = head_dh_splits(self.V1)
             slab_d = self.ws.get("slab_dh", (sk * cap * d,), torch.float32)
             ops.gemm(dl, self.W("out.weight"), slab_d, cap, d, self.V1, False, True, ops.epilogue(rows_dev=cnt),
                      split_k=sk, slab=slab_d)
@@ -779,7 +785,7 @@ class BERTEngine:
         slab = self.ws.get("vs_slab_out", (ops.wgrad_slab_numel(R, V1s, d),), torch.float32)
         ops.linear_wgrad(dl, H, self.flat.view("out.weight", grad)[v0:v1], slab,
                          db=self.flat.view("out.bias", grad)[v0:v1])
-        sk = int(max(1, min(64, -(-V1s // 2048))))
+        sk = head_dh_splits(V1s)
         slab_d = self.ws.get("vs_slab_dh", (sk * R * d,), torch.float32)
         ops.gemm(dl, Es, slab_d, R, d, V1s, False, True, ops.epilogue(), split_k=sk, slab=slab_d)
         dH = self.ws.get("vs_dH", (R, d), torch.float32)

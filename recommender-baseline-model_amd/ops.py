@@ -502,6 +502,15 @@ def vocab_head_bwd(h, E, bias, labels, ws, count, dl, rows_dev=None, dloss=None,
          ptr(count), ptr(dloss), ptr(ws), ptr(dl), ld(dl), int(voff), stream())
 
 
+def vocab_head_form(bwd, R, V1, d, cus=0):
+    """(form: 1 ping-pong / 0 lock-step, gridDim.x, gridDim.y, row tiles per y-group, dynamic LDS bytes) of the
+    vocab_head_fwd (bwd False) / vocab_head_bwd launch at these sizes (rs_vocab_head_form: host only; cus <= 0 asks
+    the device; RS_VHEAD_PP is honoured)."""
+    out = (C.c_int * 5)()
+    call("rs_vocab_head_form", int(bool(bwd)), R, V1, d, int(cus), out)
+    return tuple(out)
+
+
 def vocab_shard_lse(h, E, bias, labels, ws, lse):
     R, d = h.shape
     call("rs_vocab_shard_lse", R, E.shape[0], d, ptr(h), ld(h), ptr(E), ld(E), ptr(bias), ptr(labels), ptr(ws),

@@ -25,6 +25,18 @@ import torch.distributed as dist
 ALIGN = 128
 
 
+def shard_rows(V1, world):
+    """Rows per shard: ceil(V1 / world) rounded up to ALIGN (the last shards may be shorter, or empty)."""
+    return -(-(-(-V1 // world)) // ALIGN) * ALIGN
+
+
+def shard_range(V1, world, rank):
+    """[v0, v1): the rows of a V1-row vocabulary that shard `rank` of `world` owns (v1 == v0: none)."""
+    per = shard_rows(V1, world)
+    v0 = min(V1, rank * per)
+    return v0, min(V1, v0 + per)
+
+
 class VocabShard:
     """This rank's slice [v0, v1) of the output vocabulary (V1 = num_items + 1 rows)."""
 
@@ -32,12 +44,11 @@ class VocabShard:
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
-        per = -(-(-(-V1 // self.world)) // ALIGN) * ALIGN
-        self.v0 = min(V1, self.rank * per)
-        self.v1 = min(V1, self.v0 + per)
+        self.v0, self.v1 = shard_range(V1, self.world, self.rank)
         self.V1 = V1
         if self.v1 <= self.v0:
-            raise ValueError(f"vocabulary of {V1} rows too small for {self.world} shards of {per}")
+            raise ValueError(f"vocabulary of {V1} rows too small for {self.world} shards of "
+                             f"{shard_rows(V1, self.world)}")
 
     def owned_ranges(self, offset, d):
         """Flat-buffer float ranges of out.weight rows this rank owns (out.weight at flat offset `offset`)."""
@@ -53,7 +64,7 @@ class VocabShard:
     def gather_rows(self, full, rows_per_rank=None):
         """Make every rank's copy of a vocabulary-major tensor `full` [V1, ...] hold the owners' rows (in place):
         the reference-layout parameter (or optimizer state) for a checkpoint."""
-        per = -(-(-(-self.V1 // self.world)) // ALIGN) * ALIGN
+        per = shard_rows(self.V1, self.world)
         inner = full[0].numel() if full.dim() > 1 else 1
         buf = torch.zeros(self.world * per * inner, dtype=full.dtype, device=full.device)
         mine = torch.zeros(per * inner, dtype=full.dtype, device=full.device)
@@ -61,8 +72,7 @@ class VocabShard:
         self.all_gather(buf, mine)
         flat = full.view(-1)
         for r in range(self.world):
-            v0 = min(self.V1, r * per)
-            v1 = min(self.V1, v0 + per)
+            v0, v1 = shard_range(self.V1, self.world, r)
             if v1 > v0:
                 flat[v0 * inner:v1 * inner] = buf[r * per * inner:(r * per + v1 - v0) * inner]
         return full

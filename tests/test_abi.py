@@ -20,7 +20,7 @@ def test_header_declares_the_hot_path():
     syms = declared_symbols()
     for required in ["rs_gemm", "rs_attn_fwd", "rs_attn_bwd", "rs_embed_fwd", "rs_embed_bwd",
                      "rs_layernorm_fwd", "rs_layernorm_bwd", "rs_sampled_logits_fwd", "rs_bce_fwd",
-                     "rs_ce_fwd", "rs_adam_step"]:
+                     "rs_ce_fwd", "rs_adam_step", "rs_vocab_head_form"]:
         assert required in syms
 
 
