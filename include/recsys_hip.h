@@ -838,6 +838,16 @@ int rs_item_grad_marked(const void* ws, int nsrc, int64_t rows, int64_t table_ro
 int rs_item_grad_f32(const void* ws, int nsrc, int64_t rows, int64_t table_rows, int64_t d, const float* dx, float scale,
                      float drop_p, uint64_t salt, const uint64_t* seed_base, const float* f, const float* w1,
                      const float* w2, float* dtable, void* stream);
+/* The weighted form, one weight per entry: over an index built by rs_item_index_build(1, keys, NULL, NULL, rows * per,
+ * table_rows, d, ...) on keys int64 [rows * per],
+ *   dtable[key_e] += sum over the entries e keyed key_e of  w[e] * f[e / per]
+ * f: dtype (RS_DTYPE_F32 / RS_DTYPE_BF16) [rows][d] of row stride ldf (elements), any d; w: fp32 [rows * per];
+ * dtable fp32 [table_rows][d].  Key 0 is skipped (its w and f are not read).  One writer per table row; a key run is
+ * summed in sorted-entry order inside 32-entry chunks, a run crossing chunks as its chunk partials in chunk order
+ * (rs_item_grad_f32's rule and span pass): bitwise reproducible, no float atomics.  No [rows * per][d] buffer exists
+ * anywhere: memory grows with rows * per, never with rows * per * d.  rows * per < 2^31. */
+int rs_item_grad_weighted(const void* ws, int dtype, int64_t rows, int64_t per, int64_t table_rows, int64_t d,
+                          const void* f, int64_t ldf, const float* w, float* dtable, void* stream);
 
 /* ---- fused SASRec output head (head.hip), bf16, d in {64, 128, 256} ----------------------------
  * Forward (sas.py:87-100 + BCE of trainers/sas.py:40-49): f = LN_last(x) [f, mean, rstd saved];
@@ -872,6 +882,14 @@ int rs_sas_head_finish(int64_t nblk, const float* part, const float* divisor, fl
 int rs_sas_sample(const int64_t* user_offsets, const int64_t* user_items, int64_t n_users, int64_t item_num,
                   int64_t batch, int64_t max_len, uint64_t* seed_base, uint64_t salt, int64_t* seq, int64_t* pos,
                   int64_t* neg, void* stream);
+/* rs_sas_sample_negs: rs_sas_sample with n_negs negatives per position, neg int64 [batch][max_len][n_negs],
+ * 1 <= n_negs <= 1024.  Negative j of position (b, t) draws from the counters base + (j << 8) + a, a = 0..255, where
+ * base = seed + ((b * max_len + t) << 20) is rs_sas_sample's own; the rejection set (the window) and the never-reached
+ * linear fallback are rs_sas_sample's.  So seq, pos and neg[.][.][0] are rs_sas_sample's from the same seed and salt,
+ * bit for bit.  Draws are with replacement; padded positions are all 0; *seed_base is advanced once, first. */
+int rs_sas_sample_negs(const int64_t* user_offsets, const int64_t* user_items, int64_t n_users, int64_t item_num,
+                       int64_t batch, int64_t max_len, uint64_t* seed_base, uint64_t salt, int64_t n_negs, int64_t* seq,
+                       int64_t* pos, int64_t* neg, void* stream);
 /* rs_bert_mask: one BERT4Rec training batch as BertTrainDataset builds it (BS/dataloaders/bert.py:77-110):
  * row b's user = perm[(cursor*batch + b) mod n_users] (perm nullable = identity), its last max_len items
  * cloze-masked (prob mask_prob, a double: the reference's Python float; then 80 % [MASK] = num_items+1, 10 % a uniform item, 10 % kept;
@@ -998,6 +1016,45 @@ int rs_sas_sce_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ld
                    int64_t* keys, void* stream);
 int rs_uniform_items(const uint64_t* seed_base, uint64_t salt, int64_t item_num, int64_t K, int64_t* out,
                      void* stream);
+
+/* ---- SASRec head with N negatives per position: multi-negative BCE / gBCE (sas_gbce.hip) ----
+ * The objective, on the compact valid rows rs_sas_ce_rows_fwd leaves, with f = last_layernorm(log2feats(seq)),
+ * E = item_emb.weight (tied) and neg int64 (B, T, N):
+ *   valid r      : pos_r != 0,  n = #valid
+ *   z_r0         = <f_r, E[pos_r]>
+ *   z_rj         = <f_r, E[neg_rj]>,  j = 1..N
+ *   loss         = (1 / max(n, 1)) * sum_valid r [ beta * softplus(-z_r0) + sum_j softplus(z_rj) ]
+ *   g_r0         = s * beta * (sigmoid(z_r0) - 1),   g_rj = s * sigmoid(z_rj),   s = dloss / max(n, 1)
+ *   df_r         = g_r0 E[pos_r] + sum_j g_rj E[neg_rj]
+ *   dE[v]       += sum over (r, j = 0..N) with id_rj = v, v != 0 of  g_rj f_r
+ * The negatives are summed, not averaged: N = 1, beta = 1 is the reference's BCE term for term.  A negative id 0 is
+ * the zero row: logit exactly 0, softplus(0) in the loss, no table gradient.  Nothing is masked; equal ids in a row are
+ * separate terms; an id outside [0, V] counts as 0; a batch with no valid row gives loss 0 and all-zero gradients;
+ * table row 0 never receives a gradient.
+ * hl: [cap][d] rows of stride ldh, lab [cap], count: device int32 (NULL: cap), idx: int32 [cap], the source row of
+ * compact row r as rs_compact_rows defines it -- the negatives are read in place as neg[idx[r] * N + j]; idx == NULL
+ * is the identity (the dense fp32 form: count NULL, a row with lab 0 is no row -- its z, w, dh and keys are written
+ * as zeros).  E: [V1][d] in hl's dtype, divisor: device float (max(n, 1)), dloss: device float or NULL (1).
+ * rs_sas_gbce_fwd writes the logits z fp32 [cap][1 + N] into ws and out = {loss sum, n, sum / *divisor, negative-term
+ * sum}; the sums run in a fixed order (per-workgroup partials in double, one finishing pass, no atomics).
+ * rs_sas_gbce_bwd reads z from ws and writes dh fp32 [cap][d] (a single slab, for rs_sas_ce_rows_bwd(splits = 1)), the
+ * weights w fp32 [cap][1 + N] (the g above) and keys int64 [cap * (1 + N)] = {lab_r, neg_r1..neg_rN} per row, 0 past
+ * the count and for ids out of range: the inverted index's keys for rs_item_grad_weighted(rows = cap, per = 1 + N,
+ * f = hl).  Rows at or past *count are left untouched in every other per-row output.
+ * ws: rs_sas_gbce_ws_bytes(cap, N, d) bytes (host only; grows with cap * N, no argument for V), 16-byte aligned.
+ * dtype fp32 (any d <= 1024) or bf16 (d % 8 == 0, d <= 1024), 1 <= N <= rs_sas_gbce_max_n() (1024),
+ * cap * (1 + N) < 2^31; anything else: RS_ERR_UNSUPPORTED, nothing launched.  No allocation, no sync,
+ * graph-capturable.  A gather kernel (every row has its own 1 + N table rows): the traffic is cap * (1 + N) * d *
+ * sizeof per pass. */
+int64_t rs_sas_gbce_max_n(void);
+int64_t rs_sas_gbce_ws_bytes(int64_t cap, int64_t N, int64_t d);
+int rs_sas_gbce_fwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                    const int32_t* idx, const int32_t* count, const void* E, int64_t V1, const int64_t* neg, int64_t N,
+                    float beta, const float* divisor, void* ws, float* out, void* stream);
+int rs_sas_gbce_bwd(int dtype, int64_t cap, int64_t d, const void* hl, int64_t ldh, const int64_t* lab,
+                    const int32_t* idx, const int32_t* count, const void* E, int64_t V1, const int64_t* neg, int64_t N,
+                    float beta, const float* divisor, const float* dloss, void* ws, float* dh, float* w, int64_t* keys,
+                    void* stream);
 
 /* ---- the same sampled-softmax head for an untied output layer with a bias (sas_sce.hip; BERT4Rec's out) ----
  * E: any [V1][d] table in hl's dtype, bias: fp32 [V1] or NULL.  The definition above with

@@ -220,6 +220,12 @@ SIGNATURES = {
     "rs_sas_sce_fwd": [i32, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp],
     "rs_sas_sce_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "rs_uniform_items": [vp, u64, i64, i64, vp, vp],
+    "rs_sas_gbce_max_n": [],
+    "rs_sas_gbce_ws_bytes": [i64, i64, i64],
+    "rs_sas_gbce_fwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, f32, vp, vp, vp, vp],
+    "rs_sas_gbce_bwd": [i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp],
+    "rs_item_grad_weighted": [vp, i32, i64, i64, i64, i64, vp, i64, vp, vp, vp],
+    "rs_sas_sample_negs": [vp, vp, i64, i64, i64, i64, vp, u64, i64, vp, vp, vp, vp],
     "rs_sce_head_ws_bytes": [i32, i64, i64, i64, i32],
     "rs_sce_head_dh_splits": [i32, i64, i64, i64],
     "rs_sce_head_path": [i32, i64],
@@ -254,6 +260,7 @@ RESTYPES = {"rs_wgrad_grouped_slab_numel": C.c_int64, "rs_abi_sizeof": C.c_int64
             "rs_sas_ce_rows_nparts": C.c_int64, "rs_sas_sce_max_k": C.c_int64,
             "rs_sas_sce_ws_bytes": C.c_int64, "rs_sas_sce_dh_splits": C.c_int64,
             "rs_sce_head_ws_bytes": C.c_int64, "rs_sce_head_dh_splits": C.c_int64,
+            "rs_sas_gbce_max_n": C.c_int64, "rs_sas_gbce_ws_bytes": C.c_int64,
             "rs_eval_negs_max": C.c_int64, "rs_eval_negatives_max_draws": C.c_int64}
 
 _lib = None

@@ -26,7 +26,7 @@ ARCH = os.environ.get("RS_OFFLOAD_ARCH", "gfx950")
 # cfg2 BCE step (which launches nothing of it) measured 0.2763 ms against 0.2748 before the unit existed and 0.2737
 # with it linked last (means of six interleaved bench.py runs each).  New units go here.
 LINK_LAST = ("sas_ce.hip", "sas_sce.hip", "adam_rows.hip", "sgd.hip", "block_in_attn.hip",
-             "gradnorm.hip", "eval_loader.hip")
+             "gradnorm.hip", "eval_loader.hip", "sas_gbce.hip")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 

@@ -101,3 +101,6 @@ int rs_wgrad_grouped_pos_stats(int nprob, const rs_wgrad_problem* probs, int64_t
 }
 
 }  // extern "C"
+
+// the weighted item-table gradient (rs_item_grad_weighted): last, so that no kernel above moves
+#include "itemgrad_weighted.hip"

@@ -807,6 +807,8 @@ __device__ __forceinline__ float f32_term(const GradArgs& a, const float* __rest
 
 __global__ __launch_bounds__(256) void item_chunk_f32_kernel(GradArgs a, const float* __restrict__ dx,
                                                              const float* __restrict__ f, int64_t d) {
+  // threads CH and CH + 1 load the sentinels, and the narrowest launch has 64 threads
+  static_assert(CH + 2 <= 64, "item_chunk_f32_kernel: the sentinel threads must exist at 64 threads per workgroup");
   __shared__ uint32_t skey[CH + 2];   // [0]: the key before the chunk, [1 .. cnt]: the chunk's, [cnt + 1]: the next
   __shared__ int sm_m[CH];
   __shared__ int sm_src[CH];

@@ -231,6 +231,62 @@ __global__ __launch_bounds__(256) void rank_mean_kernel(const float* __restrict_
 
 }  // namespace smp
 
+namespace smp {
+// rs_sas_sample_negs: sas_sample_kernel with n_negs negatives per position, neg [batch][T][n_negs].  Negative j of
+// position (b, t) draws from the counters base + (j << 8) + a, a = 0 .. NA - 1, base = sas_sample_kernel's own
+// (seed + ((b * T + t) << 20)): j = 0 is that kernel's stream bit for bit, and n_negs <= 1024 keeps (j << 8) + a inside
+// the 20 bits.  Same rejection set (the window) and linear fallback; draws with replacement; padding is all 0.  The
+// (position, negative) pairs are dealt to the threads, so consecutive threads write consecutive negatives.
+__global__ __launch_bounds__(256) void sas_sample_negs_kernel(const int64_t* __restrict__ off,
+                                                              const int64_t* __restrict__ items, int64_t n_users,
+                                                              int64_t item_num, int T, int n_negs,
+                                                              const uint64_t* seed_base, uint64_t salt,
+                                                              int64_t* __restrict__ seq, int64_t* __restrict__ pos,
+                                                              int64_t* __restrict__ neg) {
+  __shared__ int64_t tab[HS];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const uint64_t seed = salt ^ ((seed_base ? *seed_base : 0ull) * 0xD1B54A32D192ED03ull);
+  const int64_t u = (int64_t)__umul64hi(splitmix64(seed ^ (0xA0761D6478BD642Full * (uint64_t)(b + 1))),
+                                        (uint64_t)n_users);
+  const int64_t s0 = off[u], L = off[u + 1] - s0;
+  const int64_t n = L < T ? L : T;          // window = the last n items (history[-max_len:])
+  const int64_t w0 = s0 + L - n;
+  const int64_t pad = T - n + 1;
+  for (int i = tid; i < HS; i += 256) tab[i] = -1;
+  __syncthreads();
+  for (int64_t i = tid; i < n; i += 256) {
+    const int64_t v = items[w0 + i];
+    int s = slot_of(v);
+    for (int p = 0; p < HS; ++p) {
+      const unsigned long long prev =
+          atomicCAS(reinterpret_cast<unsigned long long*>(&tab[s]), ~0ull, (unsigned long long)v);
+      if (prev == ~0ull || (int64_t)prev == v) break;
+      s = (s + 1) & (HS - 1);
+    }
+  }
+  __syncthreads();
+  const uint64_t V1 = (uint64_t)item_num + 1;
+  for (int t = tid; t < T; t += 256) {
+    const int64_t o = t - pad;                 // position in the window of seq[t]
+    seq[b * T + t] = o >= 0 ? items[w0 + o] : 0;
+    pos[b * T + t] = o >= 0 ? items[w0 + o + 1] : 0;
+  }
+  for (int i = tid; i < T * n_negs; i += 256) {
+    const int t = i / n_negs, j = i - t * n_negs;
+    int64_t nv = 0;
+    if (t - pad >= 0) {
+      const uint64_t base = seed + (((uint64_t)b * (uint64_t)T + (uint64_t)t) << 20) + ((uint64_t)j << 8);
+      int64_t v = (int64_t)__umul64hi(splitmix64(base), V1);
+      for (int a = 1; a < NA && contains(tab, v); ++a) v = (int64_t)__umul64hi(splitmix64(base + a), V1);
+      for (int64_t k = 0; k < (int64_t)V1 && contains(tab, v); ++k) v = (v + 1) % (int64_t)V1;   // never reached in practice
+      nv = v;
+    }
+    neg[(b * T + t) * n_negs + j] = nv;
+  }
+}
+}  // namespace smp
+
 extern "C" {
 
 int rs_sas_sample_draws(const int64_t* user_offsets, const int64_t* user_items, int64_t n_users, int64_t item_num,
@@ -251,6 +307,19 @@ int rs_sas_sample(const int64_t* user_offsets, const int64_t* user_items, int64_
                   int64_t* neg, void* stream) {
   return rs_sas_sample_draws(user_offsets, user_items, n_users, item_num, batch, max_len, seed_base, salt, seq, pos,
                              neg, nullptr, stream);
+}
+
+int rs_sas_sample_negs(const int64_t* user_offsets, const int64_t* user_items, int64_t n_users, int64_t item_num,
+                       int64_t batch, int64_t max_len, uint64_t* seed_base, uint64_t salt, int64_t n_negs, int64_t* seq,
+                       int64_t* pos, int64_t* neg, void* stream) {
+  if (n_users <= 0 || item_num <= 0 || batch <= 0 || max_len <= 0 || max_len > smp::HS / 2 || n_negs < 1 ||
+      n_negs > 1024 || !user_offsets || !user_items || !seq || !pos || !neg)
+    return RS_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (seed_base) hipLaunchKernelGGL(smp::seed_step_kernel, dim3(1), dim3(64), 0, s, seed_base);
+  hipLaunchKernelGGL(smp::sas_sample_negs_kernel, dim3((unsigned)batch), dim3(256), 0, s, user_offsets, user_items,
+                     n_users, item_num, (int)max_len, (int)n_negs, seed_base, salt, seq, pos, neg);
+  return (int)hipGetLastError();
 }
 
 int rs_bert_mask_draws(const int64_t* user_offsets, const int64_t* user_items, int64_t n_users, int64_t num_items,

@@ -324,9 +324,13 @@ class DeviceWarpSampler:
     n_outputs = 3
 
     def __init__(self, user_train, item_num, batch_size, max_len, device="cuda", num_workers=None, seed=None,
-                 shared_negs=None, proposal=None):
+                 shared_negs=None, proposal=None, negs=None):
         """user_train: list (per user) of item-id lists, as ``data_partition`` builds it.
         num_workers is accepted for signature compatibility and ignored.
+        negs=N (1 .. 1024): batches are (seq, pos, neg) with neg int64 (batch_size, max_len, N), N uniform negatives
+        per position drawn with replacement outside the row's window (rs_sas_sample_negs: neg[..., 0], seq and pos are
+        the plain sampler's from the same seed) -- the negatives of the gBCE loss.  Exclusive with shared_negs /
+        proposal (ValueError): popularity-drawn per-position negatives are not covered.
         shared_negs=K: batches are (seq, pos, cand) with cand int64 (K,) drawn uniformly with replacement from
         [1, item_num] on the device (rs_uniform_items: the same advanced step seed, its own salt) -- the candidates
         of the sampled-softmax loss, shared by the whole batch; the per-position neg goes to a private buffer.
@@ -334,6 +338,12 @@ class DeviceWarpSampler:
         (rs_alias_items, same seed, same salt); .proposal.logq is the correction the loss then needs."""
         if max_len > 512:
             raise ValueError("max_len must be <= 512")
+        if negs is not None and (shared_negs is not None or proposal is not None):
+            raise ValueError("negs (per-position negatives) cannot be combined with shared_negs / proposal (candidates "
+                             "shared by the batch)")
+        self.negs = None if negs is None else int(negs)
+        if self.negs is not None and not 1 <= self.negs <= 1024:
+            raise ValueError(f"negs must be in 1..1024, got {negs}")
         self.device = torch.device(device)
         self.offsets, self.items, self.n_users = _flatten(user_train, self.device)
         self.item_num = int(item_num)
@@ -367,11 +377,25 @@ class DeviceWarpSampler:
             else:
                 ops.uniform_items(self.seed_base, self.cand_salt, self.item_num, cand)
             return
+        if self.negs is not None:
+            if draws is not None:
+                raise ValueError("negs=N keeps no draws record")
+            if tuple(neg.shape) != tuple(seq.shape) + (self.negs,) or neg.dtype != torch.int64 or \
+                    not neg.is_contiguous():
+                raise ValueError(f"neg must be a contiguous int64 tensor of shape {tuple(seq.shape) + (self.negs,)}")
+            ops.sas_sample_negs(self.offsets, self.items, self.n_users, self.item_num, self.seed_base, self.salt, seq,
+                                pos, neg)
+            return
         ops.sas_sample(self.offsets, self.items, self.n_users, self.item_num, self.seed_base, self.salt, seq, pos, neg,
                        draws)
 
     def sample(self):
         shape = (self.batch_size, self.max_len)
+        if self.negs is not None:
+            seq, pos = (torch.empty(shape, dtype=torch.int64, device=self.device) for _ in range(2))
+            neg = torch.empty(shape + (self.negs,), dtype=torch.int64, device=self.device)
+            self.sample_into(seq, pos, neg)
+            return seq, pos, neg
         if self.shared_negs is not None:
             seq, pos = (torch.empty(shape, dtype=torch.int64, device=self.device) for _ in range(2))
             cand = torch.empty(self.shared_negs, dtype=torch.int64, device=self.device)

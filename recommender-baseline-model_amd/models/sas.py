@@ -1,6 +1,6 @@
 """SASModel wrapper -- same API as the reference ``BS/models/sas.py:6-19``."""
 from .base import BaseModel
-from .sas_model.sas import SAS
+from .sas_model.sas import SAS, gbce_beta  # noqa: F401 (gbce_beta: gBCE's positive-term power, importable here)
 
 
 class SASModel(BaseModel):
@@ -20,6 +20,9 @@ class SASModel(BaseModel):
 
     def sampled_ce_loss(self, log_seqs, pos_seqs, cand, logq=None):  # softmax over the positive + K shared candidates
         return self.sas.sampled_ce_loss(log_seqs, pos_seqs, cand, logq=logq)  # logq: the proposal's correction
+
+    def gbce_loss(self, log_seqs, pos_seqs, neg_seqs, beta=1.0):  # BCE with N negatives per position (SAS.gbce_loss)
+        return self.sas.gbce_loss(log_seqs, pos_seqs, neg_seqs, beta=beta)  # beta: gbce_beta(N, V, t), or 1
 
     def predict(self, log_seqs, item_indices):  # for inference
         return self.sas.predict(log_seqs, item_indices)

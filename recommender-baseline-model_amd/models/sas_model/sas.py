@@ -31,6 +31,9 @@ rs_sas_ce_rows_fwd -> rs_vocab_head_fwd / _bwd against the whole item table (tie
 loss="sampled_ce" (sce_forward / sce_backward): the same, with the vocabulary kernels replaced by the sampled-softmax
 head over K candidates shared by the batch (sas_sce.hip): rs_sas_sce_fwd -> rs_sas_sce_bwd (dh, the positives'
 coefficients, dEc) -> rs_item_index_build + rs_item_grad_f32 over the cap + K head keys -> rs_sas_ce_rows_bwd.
+loss="gbce" (gbce_forward / gbce_backward): the same valid-row front and back halves around the per-row gather head for
+N negatives per position (sas_gbce.hip): rs_sas_gbce_fwd -> rs_sas_gbce_bwd (dh, the weights w, the keys) ->
+rs_item_index_build + rs_item_grad_weighted over the cap * (1 + N) head entries -> rs_sas_ce_rows_bwd.
 fp32 parity mode and other widths run the generic unfused kernels: rs_embed_fwd, rs_layernorm_fwd/bwd (variant 0,
 eps 1e-8), rs_gemm (MFMA, fused bias / ReLU / dropout / residual / row-mask epilogues), rs_attn_fwd/bwd,
 rs_sampled_logits_fwd/bwd, rs_bce_*, split-K weight gradients.
@@ -48,6 +51,8 @@ from ...flat import FlatParams
 
 LN_EPS = 1e-8
 SAS_LOSSES = ("bce", "ce", "sampled_ce")
+# losses with per-position negatives beyond the reference's one: accepted alongside SAS_LOSSES
+SAS_NEG_LOSSES = ("gbce",)
 SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
 
 
@@ -77,8 +82,17 @@ class SAS(nn.Module):
         # position), "ce" (softmax cross-entropy over the whole catalogue, the item table tied as output layer) or
         # "sampled_ce" (the same softmax over the positive and sas_shared_negs candidates shared by the batch)
         self.sas_loss = str(getattr(args, "sas_loss", None) or "bce")
-        if self.sas_loss not in SAS_LOSSES:
-            raise ValueError(f"sas_loss must be one of {SAS_LOSSES}, got {self.sas_loss!r}")
+        if self.sas_loss not in SAS_LOSSES and self.sas_loss not in SAS_NEG_LOSSES:
+            raise ValueError(f"sas_loss must be one of {SAS_LOSSES + SAS_NEG_LOSSES}, got {self.sas_loss!r}")
+        # sas_loss="gbce": sas_negs = N negatives per position (required), sas_gbce_t = the calibration t in [0, 1]
+        # (0: plain multi-negative BCE, beta = 1; 1: beta = alpha; gbce_beta has the formula)
+        self.sas_negs = int(getattr(args, "sas_negs", 0) or 0)
+        self.sas_gbce_t = float(getattr(args, "sas_gbce_t", 0.0) or 0.0)
+        if self.sas_loss == "gbce":
+            if self.sas_negs < 1:
+                raise ValueError("sas_loss='gbce' needs args.sas_negs = N >= 1 (the negatives per position)")
+            if not 0.0 <= self.sas_gbce_t <= 1.0:
+                raise ValueError(f"sas_gbce_t must lie in [0, 1], got {self.sas_gbce_t}")
         # sas_loss="sampled_ce": the number of candidates (negatives shared by the whole batch) per step
         self.sas_shared_negs = int(getattr(args, "sas_shared_negs", 0) or 0)
         if self.sas_loss == "sampled_ce" and self.sas_shared_negs < 1:
@@ -174,6 +188,27 @@ class SAS(nn.Module):
         params = [p for _, p in self.named_parameters()]
         return _SASSCEFunction.apply(eng, ids, pos, cand, logq, self.training, *params)
 
+    def gbce_loss(self, log_seqs, pos_seqs, neg_seqs, beta=1.0):
+        """Scalar loss of the reference's BCE with N negatives per position, the positive term weighted by beta
+        (gSASRec's generalised BCE; differentiable; available whatever sas_loss says).  neg_seqs: int64 (B, T, N), ids
+        in [0, V]; (B, T) is taken as N = 1:
+
+            valid r : pos_r != 0,  n = #valid
+            z_r0    = <f_r, E[pos_r]>,   z_rj = <f_r, E[neg_rj]>, j = 1..N      f = last_layernorm(log2feats(seq)),
+                                                                                E = item_emb.weight (tied)
+            loss    = (1 / max(n, 1)) * sum_valid r [ beta * softplus(-z_r0) + sum_j softplus(z_rj) ]
+
+        The negatives are summed, not averaged: N = 1, beta = 1 is the reference's loss (forward + BCE) term for term.
+        A negative id 0 is the zero row (logit 0: softplus(0) in the loss, no table gradient); nothing is masked; equal
+        ids in a row are separate terms; a batch with no valid row gives loss 0 and zero gradients; row 0 of the item
+        table gets no gradient.  beta is a plain float (gbce_beta gives gSASRec's).  Call backward() before the next
+        loss call."""
+        eng = self.engine()
+        dev = self._flat.device
+        ids, pos, neg = as_ids(log_seqs, dev), as_ids(pos_seqs, dev), as_ids(neg_seqs, dev)
+        params = [p for _, p in self.named_parameters()]
+        return _SASGBCEFunction.apply(eng, ids, pos, neg, float(beta), self.training, *params)
+
     def log2feats(self, log_seqs):
         eng = self.engine()
         ids = as_ids(log_seqs, self._flat.device)
@@ -256,6 +291,44 @@ class _SASSCEFunction(torch.autograd.Function):
         ctx.saved = None
         grads = [eng.flat.view(n, grad) for n in eng.flat.names]
         return (None, None, None, None, None, None, *grads)
+
+
+class _SASGBCEFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, ids, pos, neg, beta, training, *params):
+        engine.sync_compute_weights()
+        out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
+        ctx.saved = engine.gbce_forward(ids, pos, neg, beta, training, out)
+        ctx.engine = engine
+        return out[2].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        eng = ctx.engine
+        grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
+        eng.gbce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
+        ctx.saved = None
+        grads = [eng.flat.view(n, grad) for n in eng.flat.names]
+        return (None, None, None, None, None, None, *grads)
+
+
+def gbce_beta(n_negs, num_items, t):
+    """gSASRec's positive-term power for n_negs sampled negatives out of num_items items at calibration t:
+
+        alpha = min(1, n_negs / (num_items - 1))        the sampling rate of the negatives
+        beta  = alpha * (t * (1 - 1 / alpha) + 1 / alpha)
+
+    t = 0 gives 1 (plain multi-negative BCE), t = 1 gives alpha (fully calibrated), and beta falls linearly from 1 to
+    alpha in between.  n_negs >= num_items - 1 clamps alpha (and beta) to 1."""
+    n_negs, num_items, t = int(n_negs), int(num_items), float(t)
+    if n_negs < 1 or num_items < 2:
+        raise ValueError("gbce_beta needs n_negs >= 1 and num_items >= 2")
+    if not 0.0 <= t <= 1.0:
+        raise ValueError(f"gbce_beta: t must lie in [0, 1], got {t}")
+    alpha = min(1.0, n_negs / (num_items - 1))
+    # the formula above with the product multiplied out, alpha t + (1 - t): exactly 1 at t = 0 and alpha at t = 1
+    # (alpha * (1 / alpha) need not round to 1)
+    return alpha * t + (1.0 - t)
 
 
 class SASEngine:
@@ -894,6 +967,81 @@ class SASEngine:
                 with self.side.run(after=fork, end=False):
                     head_table_grad()
         self._valid_rows_backward(s, grad, dh, sk, after_rows=after_rows)
+
+    # ---- N negatives per position: multi-negative BCE / gBCE (sas_gbce.hip) ---------------------
+    def gbce_forward(self, ids, pos, neg, beta, training, loss_out, max_labelled=None, clone_seed=True):
+        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and the BCE of the positive
+        (weighted by beta) and the row's own N negatives neg[b, t, :] (int64 (B, T, N), or (B, T) as N = 1; read in
+        place through the compaction's source-row index; SAS.gbce_loss has the definition).  loss_out = {loss sum,
+        valid count, mean, negative-term sum}.  Returns the saved state for gbce_backward.  The gbce_* buffers are
+        sized by (cap, N, d) alone; nothing here allocates per step or reads the host."""
+        d, dt = self.d, self.dt
+        if dt == torch.bfloat16 and d % 8:
+            raise ValueError(f"the bf16 gBCE head needs hidden units divisible by 8 (got {d}); "
+                             "use fp32 mode (rs_dtype='fp32') at this width")
+        if not ops.sas_gbce_ok(d, dt):
+            raise ValueError(f"the gBCE head covers hidden units up to 1024 (got {d})")
+        B, T = ids.shape
+        if neg.dim() == 2:
+            neg = neg.unsqueeze(-1)
+        if neg.dim() != 3 or tuple(neg.shape[:2]) != (B, T):
+            raise ValueError(f"neg must be (B, T, N) or (B, T) = {(B, T)}, got {tuple(neg.shape)}")
+        N, nmax = neg.shape[2], ops.sas_gbce_max_n()
+        if N < 1 or N > nmax:
+            raise ValueError(f"the gBCE head takes 1 .. {nmax} negatives per position, got {N}")
+        neg = neg if neg.is_contiguous() else neg.contiguous()
+        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
+        c = self._valid_rows_forward(s, pos, max_labelled)
+        cap = c["cap"]
+        if cap * (1 + N) >= 2 ** 31:
+            raise ValueError(f"the gBCE head needs rows * (1 + N) < 2^31 (got {cap} rows, N = {N})")
+        # the compaction's source rows (rs_compact_rows' idx, which _valid_rows_forward filled); the dense fp32 form
+        # runs on all rows: identity
+        idx = None if c["dense"] else self.ws.get("ce_idx", (cap,), torch.int32)
+        ws = self.ws.get("gbce_ws", (ops.sas_gbce_ws_numel(cap, N, d),), torch.float32)
+        ops.sas_gbce_fwd(c["hl"], c["lab"], idx, c["cnt"], cap, self.W("item_emb.weight"), neg, N, beta, c["div"], ws,
+                         loss_out)
+        c.update(neg=neg, N=N, beta=float(beta), idx=idx, gbce_ws=ws)
+        s.update(ce=c)
+        return s
+
+    def gbce_backward(self, s, grad, dloss=None):
+        """Accumulates every parameter gradient of gbce_forward's loss (times *dloss, a device scalar, if given) into
+        the flat fp32 buffer ``grad``.  The head's part of the item table's gradient -- g_rj f_r at rows pos_r and
+        neg_rj -- goes through an inverted index of its own over the cap * (1 + N) head entries (rs_item_index_build,
+        rs_item_grad_weighted: one writer per table row, no [entries][d] buffer), on the side branch beside the blocks'
+        backward (fused path; else on the main stream); the lookup part follows on that branch after the blocks'
+        backward, as in sce_backward: one writer at a time, fixed order, no float atomics."""
+        c = s["ce"]
+        d = self.d
+        f32 = torch.float32
+        g = self.ws.get
+        cap, N, hl = c["cap"], c["N"], c["hl"]
+        n = cap * (1 + N)
+        GE = self.flat.view("item_emb.weight", grad)
+        dh, w = g("gbce_dh", (1, cap, d), f32), g("gbce_w", (n,), f32)
+        keys = g("gbce_keys", (n,), torch.int64)
+        ops.sas_gbce_bwd(hl, c["lab"], c["idx"], c["cnt"], cap, self.W("item_emb.weight"), c["neg"], N, c["beta"],
+                         c["div"], dloss, c["gbce_ws"], dh, w, keys)
+        # the index's key range: past the counting sort's table limit, so that the workspace is sized by the entry
+        # count alone (as sce_backward)
+        rows = max(GE.shape[0], SCE_INDEX_ROWS)
+        iws = g("gbce_itemidx", (ops.item_index_ws_bytes(1, n, rows, d),), torch.uint8)
+
+        def head_table_grad():
+            ops.item_index_build([keys], rows, d, iws)
+            ops.item_grad_weighted(iws, cap, 1 + N, hl, w, GE, table_rows=rows)
+        after_rows = head_table_grad
+        if ops.sas_block_fused_ok(d, self.dt) and "side" in s:
+            # the fused path: these launches depend on the head alone, so they run on the side branch beside the
+            # LayerNorm and blocks' backward; the lookup part continues that branch later and the step joins it once
+            # (SideBranch, rules 2 and 3)
+            fork = self.side.mark()
+
+            def after_rows():
+                with self.side.run(after=fork, end=False):
+                    head_table_grad()
+        self._valid_rows_backward(s, grad, dh, 1, after_rows=after_rows)
 
     def enable_row_marks(self, min_rows=0):
         """Stamp the rows the inverted-index gradient writes (rs_item_grad_marked) so the optimizer can skip the

@@ -1200,6 +1200,75 @@ def alias_items(seed_base, salt, table, out):
     call("rs_alias_items", ptr(seed_base), salt, ptr(table), table.numel(), out.numel(), ptr(out), stream())
 
 
+# ---- SAS head with N negatives per position: multi-negative BCE / gBCE (sas_gbce.hip) -----------------------
+def sas_gbce_max_n():
+    """Most negatives per position the head takes (rs_sas_gbce_max_n: 1024)."""
+    return int(_lib.lib().rs_sas_gbce_max_n())
+
+
+def sas_gbce_ok(d, dtype):
+    """The dtypes / widths rs_sas_gbce_fwd / _bwd cover: fp32 at any d <= 1024, bf16 at d % 8 == 0, d <= 1024."""
+    return 1 <= d <= 1024 and (dtype == torch.float32 or (dtype == torch.bfloat16 and d % 8 == 0))
+
+
+def sas_gbce_ws_numel(cap, N, d):
+    """fp32 elements of the head's workspace (the logits [cap][1 + N] and the loss partials; host only)."""
+    n = int(_lib.lib().rs_sas_gbce_ws_bytes(cap, N, d))
+    if n < 0:
+        raise RuntimeError("rs_sas_gbce_ws_bytes: bad arguments")
+    return -(-n // 4)
+
+
+def _gbce_args(hl, lab, idx, count, cap, E, neg, N, ws):
+    d = hl.shape[1]
+    assert hl.shape[0] >= cap and lab.numel() >= cap and lab.dtype == torch.int64 and E.dtype == hl.dtype
+    assert idx is None or (idx.dtype == torch.int32 and idx.numel() >= cap)
+    assert neg.dtype == torch.int64 and neg.is_contiguous() and neg.numel() % N == 0
+    assert idx is not None or neg.numel() >= cap * N
+    assert ws.dtype == torch.float32 and ws.numel() >= sas_gbce_ws_numel(cap, N, d)
+    assert E.shape[1] == d and E.is_contiguous()
+    return d
+
+
+def sas_gbce_fwd(hl, lab, idx, count, cap, E, neg, N, beta, divisor, ws, out):
+    """The logits z [cap][1 + N] into ws, out = {loss sum, valid rows, sum / divisor, negative-term sum}
+    (rs_sas_gbce_fwd).  neg: int64, N per source row, read as neg[idx[r] * N + j] (idx None: identity)."""
+    d = _gbce_args(hl, lab, idx, count, cap, E, neg, N, ws)
+    assert out.dtype == torch.float32 and out.numel() >= 4
+    call("rs_sas_gbce_fwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(idx), ptr(count), ptr(E),
+         E.shape[0], ptr(neg), N, float(beta), ptr(divisor), ptr(ws), ptr(out), stream())
+
+
+def sas_gbce_bwd(hl, lab, idx, count, cap, E, neg, N, beta, divisor, dloss, ws, dh, w, keys):
+    """dh fp32 [cap][d], the weights w fp32 [cap][1 + N], keys int64 [cap * (1 + N)] (rs_sas_gbce_bwd)."""
+    d = _gbce_args(hl, lab, idx, count, cap, E, neg, N, ws)
+    assert dh.dtype == torch.float32 and dh.is_contiguous() and dh.numel() >= cap * d
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() >= cap * (1 + N)
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and keys.numel() >= cap * (1 + N)
+    call("rs_sas_gbce_bwd", dtype_code(hl), cap, d, ptr(hl), ld(hl), ptr(lab), ptr(idx), ptr(count), ptr(E),
+         E.shape[0], ptr(neg), N, float(beta), ptr(divisor), ptr(dloss), ptr(ws), ptr(dh), ptr(w), ptr(keys), stream())
+
+
+def item_grad_weighted(ws, rows, per, f, w, dtable, table_rows=None):
+    """dtable[key_e] += sum_e w[e] * f[e // per] over the index built on rows * per keys (item_index_build([keys], ...)):
+    rs_item_grad_weighted.  f: fp32 / bf16 (rows, d) rows (row stride may exceed d), w fp32 [rows * per].
+    table_rows: the key range the index was built with, where that is not the table's row count."""
+    d = dtable.shape[1]
+    assert f.shape[0] >= rows and f.shape[1] == d and f.stride(1) == 1
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() >= rows * per
+    assert dtable.dtype == torch.float32 and dtable.is_contiguous()
+    call("rs_item_grad_weighted", ptr(ws), dtype_code(f), rows, per,
+         dtable.shape[0] if table_rows is None else table_rows, d, ptr(f), ld(f), ptr(w), ptr(dtable), stream())
+
+
+def sas_sample_negs(user_offsets, user_items, n_users, item_num, seed_base, salt, seq, pos, neg):
+    """rs_sas_sample_negs: the next batch with neg int64 (batch, max_len, n_negs)."""
+    B, T = seq.shape
+    assert neg.dim() == 3 and neg.shape[:2] == (B, T) and neg.dtype == torch.int64 and neg.is_contiguous()
+    call("rs_sas_sample_negs", ptr(user_offsets), ptr(user_items), n_users, item_num, B, T, ptr(seed_base), salt,
+         neg.shape[2], ptr(seq), ptr(pos), ptr(neg), stream())
+
+
 def sas_head_finish(part, divisor, out):
     """Loss statistics out[0..3] from the head's BCE partials part[nblk][3] (one workgroup)."""
     call("rs_sas_head_finish", part.numel() // 3, ptr(part), ptr(divisor), ptr(out), stream())

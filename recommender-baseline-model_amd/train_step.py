@@ -72,8 +72,8 @@ class FusedTrainStep:
             loss = getattr(model.sas, "sas_loss", "bce") if kind == "sas" else None
             if kind == "bert" and getattr(model.bert, "bert_loss", "ce") == "sampled_ce":
                 loss = "sampled_ce"
-        if kind == "sas" and loss not in ("bce", "ce", "sampled_ce"):
-            raise ValueError(f"loss must be 'bce', 'ce' or 'sampled_ce', got {loss!r}")
+        if kind == "sas" and loss not in ("bce", "ce", "sampled_ce", "gbce"):
+            raise ValueError(f"loss must be 'bce', 'ce', 'sampled_ce' or 'gbce', got {loss!r}")
         if kind != "sas" and loss not in (None, "sampled_ce"):
             raise ValueError(f"loss={loss!r} needs a SAS model (a BERT step takes loss='sampled_ce', or None for the "
                              "model's own bert_loss: its cross-entropy by default)")
@@ -106,8 +106,10 @@ class FusedTrainStep:
                 why = f"l2_emb must be 0 (got {model.sas.l2_emb}): the regulariser gives every row a gradient"
             if why:
                 raise ValueError(f"FusedTrainStep(table_optim='sparse'): {why}")
-        if loss in ("ce", "sampled_ce") and dp_on:
+        if loss in ("ce", "sampled_ce", "gbce") and dp_on:
             raise ValueError(f"FusedTrainStep(loss={loss!r}) runs on a single device (data parallel is not covered)")
+        if loss == "gbce" and shard_rows == "on":
+            raise ValueError("FusedTrainStep(loss='gbce') runs on a single device (shard_rows='on' is not covered)")
         if kind == "bert" and loss == "sampled_ce" and vocab_shard:
             raise ValueError("FusedTrainStep(loss='sampled_ce') runs on a single device (vocab_shard is not covered)")
         if vocab_shard and not (dp_on and kind == "bert"):
@@ -118,8 +120,10 @@ class FusedTrainStep:
 
     def __init__(self, model, lr=1e-3, weight_decay=0.0, process_group=None, dp=None, max_labelled=None,
                  bucket_numel=None, overlap=None, vocab_shard=False, sparse_rows="auto", shard_rows="auto", loss=None,
-                 logq=None, table_optim="dense", optimizer="adam", momentum=0.0, max_grad_norm=None):
+                 logq=None, table_optim="dense", optimizer="adam", momentum=0.0, max_grad_norm=None, gbce_beta=None):
         """model: rbm_amd SASModel or BERTModel on a CUDA device.
+        gbce_beta (loss="gbce" only): the positive term's weight beta, a plain float; None (default) =
+        gbce_beta(args.sas_negs, num_items, args.sas_gbce_t) from the model's args (1 at the default t = 0).
         max_grad_norm: None (default: the step's launches are exactly those of a step built without the argument), or
         a positive number c: every step clips its gradient by global norm, torch.nn.utils.clip_grad_norm_(
         model.parameters(), c) between the backward and the optimizer -- ``grad_norm`` (the total norm BEFORE
@@ -173,7 +177,10 @@ class FusedTrainStep:
         catalogue with the item table as output layer, SASModel.ce_loss); None = the model's args.sas_loss.  With
         "ce" the batch's neg plays no part and may be None; single device only.  "sampled_ce": the same softmax over
         the positive and K candidates shared by the whole batch (SASModel.sampled_ce_loss); the batch is (seq, pos,
-        cand) with cand int64 (K,); single device, steps_per_graph = 1.
+        cand) with cand int64 (K,); single device, steps_per_graph = 1.  "gbce": the reference's BCE with N negatives
+        per position and the positive term weighted by beta (SASModel.gbce_loss); the batch is (seq, pos, neg) with
+        neg int64 (B, T, N), N = the model's args.sas_negs (a (B, T) neg is N = 1); single device, steps_per_graph =
+        1, no shard_rows; table_optim="sparse" touches seq | pos | neg.
         loss (BERT): None = the model's args.bert_loss (the reference's cross-entropy over the whole vocabulary by
         default), or "sampled_ce" (the softmax over the label and K candidates shared by the whole batch,
         BERTModel.sampled_ce_loss; the batch is (tokens, labels, cand)): single device, steps_per_graph = 1, no
@@ -198,6 +205,20 @@ class FusedTrainStep:
         self.optimizer, self.momentum, shard_rows, loss, self.max_grad_norm, self.dp = self._check_args(
             weight_decay, dp, vocab_shard, shard_rows, loss, logq, table_optim, optimizer, momentum, max_grad_norm)
         self.loss, self.table_optim, self._logq_arg = loss, table_optim, logq
+        self.gbce_negs = self.gbce_beta = None
+        if loss == "gbce":
+            from .models.sas_model.sas import gbce_beta as _gbce_beta
+            self.gbce_negs = int(getattr(model.sas, "sas_negs", 0) or 0)
+            if self.gbce_negs < 1:
+                raise ValueError("FusedTrainStep(loss='gbce') needs the model's args.sas_negs = N >= 1")
+            if gbce_beta is None:
+                gbce_beta = _gbce_beta(self.gbce_negs, model.sas.item_num, getattr(model.sas, "sas_gbce_t", 0.0))
+            if isinstance(gbce_beta, bool) or not isinstance(gbce_beta, (int, float)) or \
+                    not math.isfinite(gbce_beta) or gbce_beta < 0:
+                raise ValueError(f"gbce_beta must be a finite number >= 0, got {gbce_beta!r}")
+            self.gbce_beta = float(gbce_beta)
+        elif gbce_beta is not None:
+            raise ValueError(f"gbce_beta needs loss='gbce' (got loss={loss!r})")
         self.logq = logq if isinstance(logq, torch.Tensor) else None
         self.engine = model.sas.engine() if self.kind == "sas" else model.engine()
         if self.kind == "bert":
@@ -316,7 +337,7 @@ class FusedTrainStep:
         # gradient is sparse again, but its head rows come from the fp32 index launch, which stamps nothing: off too.
         # (SAS: its head rows land in the marked table itself.  BERT's sampled head writes out.weight / out.bias, not the
         # marked token table, whose rows still come from the stamping launch alone: the marks stay on.)
-        tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce")
+        tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce", "gbce")
         # A sparse table takes no marks either: its untouched rows are not swept at all.
         sparse = table_optim == "sparse"
         no_marks = tied_head or sparse or self.optimizer == "sgd"       # (the marked sweeps are Adam's)
@@ -334,7 +355,7 @@ class FusedTrainStep:
             def tab(name):
                 shp = f.shapes[name]
                 return (f.offsets[name], shp[0], shp[1] if len(shp) > 1 else 1)
-            if self.kind == "sas":      # bce: seq | pos | neg; sampled_ce: seq | pos | cand
+            if self.kind == "sas":      # bce, gbce: seq | pos | neg (flattened); sampled_ce: seq | pos | cand
                 self._sparse_tables = [((0, 1, 2), [tab("item_emb.weight")])]
             else:                       # tokens; labels | cand
                 self._sparse_tables = [((0,), [tab("bert.embedding.token.weight")]),
@@ -482,6 +503,11 @@ class FusedTrainStep:
             saved = eng.sce_forward(seq, pos, cand, True, self.loss_out, max_labelled=self.max_labelled,
                                     clone_seed=False, logq=self.logq)
             eng.sce_backward(saved, self.flat.grad)
+        elif self.kind == "sas" and self.loss == "gbce":
+            seq, pos, neg = batch
+            saved = eng.gbce_forward(seq, pos, self._gbce_neg(seq, neg), self.gbce_beta, True, self.loss_out,
+                                     max_labelled=self.max_labelled, clone_seed=False)
+            eng.gbce_backward(saved, self.flat.grad)
         elif self.kind == "sas":
             seq, pos, neg = batch
             pl, nl, saved = eng.forward(seq, pos, neg, True, clone_seed=False, fuse_head=eng.fused_head,
@@ -672,6 +698,16 @@ class FusedTrainStep:
             self.opt.step_keep_early(rng, max_wg=self.EARLY_HEAD_ADAM_WG)
         self._early_forked = True
 
+    def _gbce_neg(self, seq, neg):
+        """loss="gbce": the batch's neg as (B, T, N) with N = the model's sas_negs ((B, T) is N = 1)."""
+        if neg is None or neg.dim() not in (2, 3) or tuple(neg.shape[:2]) != tuple(seq.shape):
+            raise ValueError(f"loss='gbce' needs neg of shape (B, T, N) with (B, T) = {tuple(seq.shape)}")
+        n = 1 if neg.dim() == 2 else neg.shape[2]
+        if n != self.gbce_negs:
+            raise ValueError(f"loss='gbce': the batch has {n} negs per position, the model's sas_negs is "
+                             f"{self.gbce_negs}")
+        return neg
+
     def _batch(self, batch):
         """loss="ce": neg is ignored and may be None -- pos stands in, so the (seq, pos, neg) buffers keep their form."""
         if self.loss == "ce" and (len(batch) == 2 or batch[2] is None):
@@ -836,6 +872,9 @@ class FusedTrainStep:
         if S > 1 and self.loss == "sampled_ce":
             raise ValueError("loss='sampled_ce' needs steps_per_graph = 1: cand has another shape than seq / pos, "
                              "and the unrolled graph takes one packed buffer")
+        if S > 1 and self.loss == "gbce":
+            raise ValueError("loss='gbce' needs steps_per_graph = 1: neg has another shape than seq / pos, and the "
+                             "unrolled graph takes one packed buffer")
         if S > 1 and self.dp and not self.graph_collectives:
             raise ValueError("steps_per_graph > 1 under DP needs the all-reduce inside the graph (graph_collectives)")
         self.steps_per_graph = S
@@ -1073,10 +1112,21 @@ class FusedTrainStep:
             want = 3
         if getattr(sampler, "n_outputs", None) != want:
             raise ValueError(f"the {self.kind} step needs a sampler producing {want} tensors")
+        if self.loss == "gbce" and getattr(sampler, "negs", None) != self.gbce_negs:
+            raise ValueError(f"loss='gbce' needs a sampler with negs={self.gbce_negs} (the model's sas_negs); this "
+                             f"one has negs={getattr(sampler, 'negs', None)}")
+        if self.loss != "gbce" and getattr(sampler, "negs", None) is not None:
+            raise ValueError(f"a sampler with negs={sampler.negs} feeds loss='gbce' (this step's loss is "
+                             f"{self.loss!r})")
         S = self._unroll_check(steps_per_graph)
         self.sampler = sampler
         shape = (sampler.batch_size, sampler.max_len)
-        if self.loss == "sampled_ce":
+        if self.loss == "gbce":
+            # no packed buffer: neg has another shape (replay_packed then goes through replay())
+            self.packed = None
+            self.static = [torch.zeros(n, dtype=torch.int64, device=self.flat.device)
+                           for n in (shape, shape, shape + (self.gbce_negs,))]
+        elif self.loss == "sampled_ce":
             K = getattr(sampler, "shared_negs", None)
             if not K:
                 raise ValueError("loss='sampled_ce' needs a sampler with shared_negs=K")
