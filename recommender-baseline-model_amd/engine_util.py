@@ -33,6 +33,7 @@ def require_cuda(device):
 
 
 NEG_DISTS = ("uniform", "popular")
+SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
 
 
 def neg_dist_args(args, prefix, loss):
@@ -130,7 +131,8 @@ class SideBranch:
        before Adam; BERT cfg3, token index first, ~7 us before the embedding and ~12 us at the token gradient's
        queue hop (three interleaved rounds: 1.4145 / 1.4142 / 1.4149 -> 1.3983 / 1.4052 / 1.3978 ms/step).
     3. One writer per table.  All side work on one table goes to the SAME branch, so the table has one writer at a
-       time in a fixed order (sce_backward's head rows, then the lookup rows, joined once).
+       time in a fixed order (a SAS row head's table_grad or BERT sce_backward's head rows, then the lookup rows,
+       joined once).
     4. Distinct streams.  The side stream is never the stream it forks from: new_stream() draws it apart from the
        streams given, and run() asserts it against the current one."""
 

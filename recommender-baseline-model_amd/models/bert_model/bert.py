@@ -36,13 +36,12 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine_util import (SideBranch, Workspace, as_ids, check_logq, compute_dtype, neg_dist_args, require_cuda,
-                            site_salt)
+from ...engine_util import (SCE_INDEX_ROWS, SideBranch, Workspace, as_ids, check_logq, compute_dtype, neg_dist_args,
+                            require_cuda, site_salt)
 from ...flat import ALIGN, FlatParams
 
 LN_EPS = 1e-6  # utils/layer_norm.py:8
 BERT_LOSSES = ("ce", "sampled_ce")
-SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
 
 
 def head_dh_splits(V1):

@@ -25,13 +25,14 @@ weight / bias / LayerNorm-affine gradient
 (rs_wgrad_grouped_pos_stats, with the positional table's gradient and the loss statistics) beside the item-table
 gradient by inverted index (rs_item_index_build on a side stream during the forward, rs_item_grad), then the fused
 Adam (rs_adam_prepare_step_loss).
-loss="ce" (ce_forward / ce_backward): the blocks without the in-block head, then on the rows with pos != 0 only
+The tied losses are row heads (heads.py) between rows_forward / rows_backward's shared halves.
+loss="ce" (CEHead): the blocks without the in-block head, then on the rows with pos != 0 only
 rs_sas_ce_rows_fwd -> rs_vocab_head_fwd / _bwd against the whole item table (tied) -> rs_linear_wgrad (dE) -> rs_gemm
 (dh) -> rs_sas_ce_rows_bwd, and the blocks' backward with the item index over the input ids alone.
-loss="sampled_ce" (sce_forward / sce_backward): the same, with the vocabulary kernels replaced by the sampled-softmax
+loss="sampled_ce" (SampledCEHead): the same, with the vocabulary kernels replaced by the sampled-softmax
 head over K candidates shared by the batch (sas_sce.hip): rs_sas_sce_fwd -> rs_sas_sce_bwd (dh, the positives'
 coefficients, dEc) -> rs_item_index_build + rs_item_grad_f32 over the cap + K head keys -> rs_sas_ce_rows_bwd.
-loss="gbce" (gbce_forward / gbce_backward): the same valid-row front and back halves around the per-row gather head for
+loss="gbce" (GBCEHead): the same valid-row front and back halves around the per-row gather head for
 N negatives per position (sas_gbce.hip): rs_sas_gbce_fwd -> rs_sas_gbce_bwd (dh, the weights w, the keys) ->
 rs_item_index_build + rs_item_grad_weighted over the cap * (1 + N) head entries -> rs_sas_ce_rows_bwd.
 fp32 parity mode and other widths run the generic unfused kernels: rs_embed_fwd, rs_layernorm_fwd/bwd (variant 0,
@@ -45,15 +46,15 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine_util import (SideBranch, Workspace, as_ids, check_logq, compute_dtype, neg_dist_args, require_cuda,
-                            site_salt)
+from ...engine_util import (SCE_INDEX_ROWS, SideBranch, Workspace, as_ids, compute_dtype,  # noqa: F401 (re-exported)
+                            neg_dist_args, require_cuda, site_salt)
 from ...flat import FlatParams
+from .heads import CEHead, GBCEHead, SampledCEHead, gbce_beta  # noqa: F401 (gbce_beta: re-exported)
 
 LN_EPS = 1e-8
 SAS_LOSSES = ("bce", "ce", "sampled_ce")
 # losses with per-position negatives beyond the reference's one: accepted alongside SAS_LOSSES
 SAS_NEG_LOSSES = ("gbce",)
-SCE_INDEX_ROWS = 32769      # one past the largest table the item index counting-sorts (itemgrad.hip)
 
 
 class PointWiseFeedForward(nn.Module):
@@ -149,6 +150,15 @@ class SAS(nn.Module):
         params = [p for _, p in self.named_parameters()]
         return _SASFunction.apply(eng, ids, pos, neg, self.training, *params)
 
+    def _rows_loss(self, head, log_seqs, pos_seqs, own_ids=(), rest=()):
+        """A row head's loss (heads.py); own_ids: the head's own id tensors (cand / neg), rest: its other extras."""
+        eng = self.engine()
+        dev = self._flat.device
+        ids, pos = as_ids(log_seqs, dev), as_ids(pos_seqs, dev)
+        extra = (*(as_ids(x, dev) for x in own_ids), *rest)
+        params = [p for _, p in self.named_parameters()]
+        return _SASRowsFunction.apply(eng, head, ids, pos, extra, self.training, *params)
+
     def ce_loss(self, log_seqs, pos_seqs):
         """Scalar loss of the tied full-catalogue objective (differentiable; available whatever sas_loss says):
 
@@ -158,11 +168,7 @@ class SAS(nn.Module):
         the mean over the positions with pos != 0.  The padding row of the item table gets no gradient.  A batch
         with no valid position gives loss 0 and all-zero gradients (torch gives NaN there).  The head's buffers are
         the engine's workspace: call backward() before the next ce_loss()."""
-        eng = self.engine()
-        dev = self._flat.device
-        ids, pos = as_ids(log_seqs, dev), as_ids(pos_seqs, dev)
-        params = [p for _, p in self.named_parameters()]
-        return _SASCEFunction.apply(eng, ids, pos, self.training, *params)
+        return self._rows_loss(CEHead(), log_seqs, pos_seqs)
 
     def sampled_ce_loss(self, log_seqs, pos_seqs, cand, logq=None):
         """Scalar loss of the sampled softmax over batch-shared candidates (differentiable; available whatever
@@ -182,11 +188,7 @@ class SAS(nn.Module):
         logq: fp32 (V + 1,) on the device, the log of the distribution the candidates were drawn from
         (ItemProposal.logq): the logQ correction, z_r0 -= logq[pos_r] and z_rj -= logq[cand_j].  It is a constant
         of the loss (no gradient); entry 0 is never read.  None: no correction."""
-        eng = self.engine()
-        dev = self._flat.device
-        ids, pos, cand = as_ids(log_seqs, dev), as_ids(pos_seqs, dev), as_ids(cand, dev)
-        params = [p for _, p in self.named_parameters()]
-        return _SASSCEFunction.apply(eng, ids, pos, cand, logq, self.training, *params)
+        return self._rows_loss(SampledCEHead(), log_seqs, pos_seqs, (cand,), (logq,))
 
     def gbce_loss(self, log_seqs, pos_seqs, neg_seqs, beta=1.0):
         """Scalar loss of the reference's BCE with N negatives per position, the positive term weighted by beta
@@ -203,11 +205,7 @@ class SAS(nn.Module):
         ids in a row are separate terms; a batch with no valid row gives loss 0 and zero gradients; row 0 of the item
         table gets no gradient.  beta is a plain float (gbce_beta gives gSASRec's).  Call backward() before the next
         loss call."""
-        eng = self.engine()
-        dev = self._flat.device
-        ids, pos, neg = as_ids(log_seqs, dev), as_ids(pos_seqs, dev), as_ids(neg_seqs, dev)
-        params = [p for _, p in self.named_parameters()]
-        return _SASGBCEFunction.apply(eng, ids, pos, neg, float(beta), self.training, *params)
+        return self._rows_loss(GBCEHead(beta), log_seqs, pos_seqs, (neg_seqs,))
 
     def log2feats(self, log_seqs):
         eng = self.engine()
@@ -255,12 +253,14 @@ class _SASFunction(torch.autograd.Function):
         return (None, None, None, None, None, *grads)
 
 
-class _SASCEFunction(torch.autograd.Function):
+class _SASRowsFunction(torch.autograd.Function):
+    """The loss of a row head (heads.py) through SASEngine.rows_forward / rows_backward."""
+
     @staticmethod
-    def forward(ctx, engine, ids, pos, training, *params):
+    def forward(ctx, engine, head, ids, pos, extra, training, *params):
         engine.sync_compute_weights()
         out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
-        ctx.saved = engine.ce_forward(ids, pos, training, out)
+        ctx.saved = engine.rows_forward(head, ids, pos, extra, training, out)
         ctx.engine = engine
         return out[2].clone()
 
@@ -268,67 +268,10 @@ class _SASCEFunction(torch.autograd.Function):
     def backward(ctx, dloss):
         eng = ctx.engine
         grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
-        eng.ce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
-        ctx.saved = None
-        grads = [eng.flat.view(n, grad) for n in eng.flat.names]
-        return (None, None, None, None, *grads)
-
-
-class _SASSCEFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, engine, ids, pos, cand, logq, training, *params):
-        engine.sync_compute_weights()
-        out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
-        ctx.saved = engine.sce_forward(ids, pos, cand, training, out, logq=logq)
-        ctx.engine = engine
-        return out[2].clone()
-
-    @staticmethod
-    def backward(ctx, dloss):
-        eng = ctx.engine
-        grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
-        eng.sce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
+        eng.rows_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
         ctx.saved = None
         grads = [eng.flat.view(n, grad) for n in eng.flat.names]
         return (None, None, None, None, None, None, *grads)
-
-
-class _SASGBCEFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, engine, ids, pos, neg, beta, training, *params):
-        engine.sync_compute_weights()
-        out = torch.zeros(4, dtype=torch.float32, device=engine.dev)
-        ctx.saved = engine.gbce_forward(ids, pos, neg, beta, training, out)
-        ctx.engine = engine
-        return out[2].clone()
-
-    @staticmethod
-    def backward(ctx, dloss):
-        eng = ctx.engine
-        grad = torch.zeros(eng.flat.numel, dtype=torch.float32, device=eng.flat.device)
-        eng.gbce_backward(ctx.saved, grad, dloss=dloss.contiguous().float().reshape(1))
-        ctx.saved = None
-        grads = [eng.flat.view(n, grad) for n in eng.flat.names]
-        return (None, None, None, None, None, None, *grads)
-
-
-def gbce_beta(n_negs, num_items, t):
-    """gSASRec's positive-term power for n_negs sampled negatives out of num_items items at calibration t:
-
-        alpha = min(1, n_negs / (num_items - 1))        the sampling rate of the negatives
-        beta  = alpha * (t * (1 - 1 / alpha) + 1 / alpha)
-
-    t = 0 gives 1 (plain multi-negative BCE), t = 1 gives alpha (fully calibrated), and beta falls linearly from 1 to
-    alpha in between.  n_negs >= num_items - 1 clamps alpha (and beta) to 1."""
-    n_negs, num_items, t = int(n_negs), int(num_items), float(t)
-    if n_negs < 1 or num_items < 2:
-        raise ValueError("gbce_beta needs n_negs >= 1 and num_items >= 2")
-    if not 0.0 <= t <= 1.0:
-        raise ValueError(f"gbce_beta: t must lie in [0, 1], got {t}")
-    alpha = min(1.0, n_negs / (num_items - 1))
-    # the formula above with the product multiplied out, alpha t + (1 - t): exactly 1 at t = 0 and alpha at t = 1
-    # (alpha * (1 / alpha) need not round to 1)
-    return alpha * t + (1.0 - t)
 
 
 class SASEngine:
@@ -411,7 +354,7 @@ class SASEngine:
         and backward run as one pass per token inside the last block's output kernel (rs_sas_block_out with a head); the
         returned pl / nl are filled by then.  The first block's input kernel counts the valid positions (the BCE
         divisor) for it; head_divisor (device scalar, data parallel: 1) replaces that count and must be the divisor
-        later passed to backward.  ce (ce_forward): the blocks only -- no last LayerNorm, no sampled head; the
+        later passed to backward.  ce (rows_forward): the blocks only -- no last LayerNorm, no sampled head; the
         side branch indexes the input ids alone (neg plays no part)."""
         B, T = ids.shape
         M, d, H, Dh, L = B * T, self.d, self.H, self.Dh, self.L
@@ -735,7 +678,7 @@ class SASEngine:
             ops.item_grad(iws, n, M, dx, math.sqrt(d), p, self.salt["emb"], sb, f, w1, w2,
                           G("item_emb.weight"), marks=getattr(self, "row_marks", None) if n == 3 else None)
 
-    # ---- tied full-catalogue cross-entropy head ---------------------------------------
+    # ---- the row heads (heads.py): ce, sampled_ce, gbce -----------------------------------
     @property
     def ce_rows_fused(self):
         """True when the CE head's row-local work runs in the two sas_ce.hip launches (bf16, d in {64, 128});
@@ -743,7 +686,7 @@ class SASEngine:
         return ops.sas_ce_rows_ok(self.d, self.dt) and os.environ.get("RS_SAS_CE_ROWS", "1") != "0"
 
     def _valid_rows_forward(self, s, pos, max_labelled):
-        """The last LayerNorm on the rows with pos != 0, compacted (the front half of both softmax heads): hl [cap][d],
+        """The last LayerNorm on the rows with pos != 0, compacted (the front half of every row head): hl [cap][d],
         lab [cap], the device row count and the mean's divisor max(count, 1), in the engine's ce_* buffers."""
         d, dt = self.d, self.dt
         M = s["B"] * s["T"]
@@ -779,72 +722,35 @@ class SASEngine:
         return dict(cap=cap, V1=V1, V1p=V1p, rank=rank, cnt=cnt, hl=hl, lab=lab, div=div, mu=mu, rs=rs,
                     rows_fused=rows_fused, dense=dense)
 
-    def ce_forward(self, ids, pos, training, loss_out, max_labelled=None, clone_seed=True):
-        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and CrossEntropy(ignore_index=0)
-        of the logits against the whole item table (tied; class 0 is the zero padding row), never materialised in
-        bf16.  loss_out (fp32 [>= 3], device) = {loss sum, valid count, mean}; a batch without a valid row gives
-        mean 0.  max_labelled: upper bound on the valid rows (sizes the compact buffers; default B*T; rows past it
-        are dropped as rs_compact_rows does).  Returns the saved state for ce_backward.  Buffers are the engine's
-        workspace; nothing here allocates per step or reads the host."""
-        d, dt = self.d, self.dt
-        if dt == torch.bfloat16 and d % 8:
-            raise ValueError(f"the bf16 cross-entropy head needs hidden units divisible by 8 (got {d}); "
-                             "use fp32 mode (rs_dtype='fp32') at this width")
+    def rows_forward(self, head, ids, pos, extra, training, loss_out, max_labelled=None, clone_seed=True):
+        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and the row head's loss (heads.py;
+        extra: the head's own batch tensors).  loss_out (fp32 [>= 3], device) = {loss sum, valid count, mean}; a batch
+        without a valid row gives mean 0.  max_labelled: upper bound on the valid rows (sizes the compact buffers;
+        default B*T; rows past it are dropped as rs_compact_rows does).  Returns the saved state for rows_backward.
+        Buffers are the engine's workspace; nothing here allocates per step or reads the host."""
+        extra = head.prepare(self, ids, pos, *extra)
         _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
-        f32 = torch.float32
-        g = self.ws.get
         c = self._valid_rows_forward(s, pos, max_labelled)
-        cap, V1, V1p, cnt, hl, lab, div = (c[k] for k in ("cap", "V1", "V1p", "cnt", "hl", "lab", "div"))
-        E = self.W("item_emb.weight")
-        if dt == torch.bfloat16:
-            wce = g("ce_vce", (ops.vocab_ce_ws_numel(cap, V1),), f32)
-            fwd = ops.vocab_head_fwd if ops.vocab_head_supported(d) else ops.vocab_ce_fwd
-            fwd(hl, E, None, lab, wce, loss_out, rows_dev=cnt, count_override=div)
-            dl = None
-        else:
-            dl = g("ce_logits", (cap, V1p), f32)[:, :V1]          # the logits, then dlogits in place
-            ops.linear_fwd(hl, E, dl, rows_dev=cnt)
-            wce = g("ce_wce", (3 * cap,), f32)
-            ops.ce_fwd(dl, lab, wce, loss_out, div, rows_dev=cnt)
-        c.update(wce=wce, dl=dl)
+        c.update(head=head)
+        head.forward(self, c, extra, loss_out)
         s.update(ce=c)
         return s
 
-    def ce_backward(self, s, grad, dloss=None):
-        """Accumulates every parameter gradient of ce_forward's loss (times *dloss, a device scalar, if given) into
-        the flat fp32 buffer ``grad``.  The item table's gradient has two parts: the dense dlogits^T f over all
-        rows (rs_linear_wgrad's fixed-order split-K, row 0 cleared afterwards: the padding row gets no gradient),
-        written on the main stream BEFORE the blocks' backward, and the lookup part by the inverted index over the
-        input ids (rs_item_grad, one writer per row), which the fused path runs on the side stream only after the
-        blocks' backward: one writer at a time, fixed order, no float atomics."""
-        c = s["ce"]
-        d, dt = self.d, self.dt
-        f32 = torch.float32
-        g = self.ws.get
-        G = lambda n: self.flat.view(n, grad)  # noqa: E731
-        cap, V1, cnt, hl, lab = c["cap"], c["V1"], c["cnt"], c["hl"], c["lab"]
-        E = self.W("item_emb.weight")
-        if dt == torch.bfloat16:
-            dl = g("ce_dlogits", (cap, c["V1p"]), dt)[:, :V1]     # the one (cap, V+1) buffer of the bf16 path
-            bwd = ops.vocab_head_bwd if ops.vocab_head_supported(d) else ops.vocab_ce_bwd
-            bwd(hl, E, None, lab, c["wce"], c["div"], dl, rows_dev=cnt, dloss=dloss)
-        else:
-            dl = c["dl"]
-            ops.ce_bwd(dl, lab, c["div"], dloss, c["wce"], dl, rows_dev=cnt)
-        GE = G("item_emb.weight")
-        slab = g("ce_slab_dE", (ops.wgrad_slab_numel(cap, V1, d),), f32)
-        ops.linear_wgrad(dl, hl, GE, slab, rows_dev=cnt, accumulate=True)
-        GE[0].zero_()                              # class 0 is the padding row: no gradient (padding_idx)
-        # dh = dlogits E: a contraction over the whole catalogue with few rows -- split-K into fp32 slabs
-        sk = int(max(1, min(64, -(-V1 // 2048))))
-        slab_d = g("ce_slab_dh", (sk * cap * d,), f32)
-        ops.gemm(dl, E, slab_d, cap, d, V1, False, True, ops.epilogue(rows_dev=cnt), split_k=sk, slab=slab_d)
-        self._valid_rows_backward(s, grad, slab_d, sk)
+    def rows_backward(self, s, grad, dloss=None):
+        """Accumulates every parameter gradient of rows_forward's loss (times *dloss, a device scalar, if given) into
+        the flat fp32 buffer ``grad``: the head's backward, then the shared back half."""
+        slab_d, sk, table_grad = s["ce"]["head"].backward(self, s, grad, dloss)
+        self._valid_rows_backward(s, grad, slab_d, sk, table_grad)
 
-    def _valid_rows_backward(self, s, grad, slab_d, sk, after_rows=None):
+    def _valid_rows_backward(self, s, grad, slab_d, sk, table_grad=None):
         """From dh on the compact rows (fp32 slab_d [sk][cap][d], summed in split order): the last LayerNorm's
-        backward scattered to all rows, the blocks' backward and the lookup part of the item table's gradient (the
-        back half of both softmax heads).  after_rows(): called once the LayerNorm backward has been issued."""
+        backward scattered to all rows, the blocks' backward and the lookup part of the item table's gradient by the
+        inverted index over the input ids (the back half of every row head).  table_grad(): the head's own rows of that
+        gradient, launches that depend on the head alone.  On the fused path they run on the side branch beside the
+        LayerNorm and blocks' backward, forked before the LayerNorm backward and issued after it; the lookup part
+        continues that branch after the blocks' backward and the step joins it once (SideBranch, rules 2 and 3): one
+        writer at a time, fixed order, no float atomics.  Elsewhere they follow the LayerNorm backward on the main
+        stream."""
         c = s["ce"]
         B, T, p, ids = s["B"], s["T"], s["p"], s["ids"]
         M, d = B * T, self.d
@@ -856,6 +762,7 @@ class SASEngine:
         GE = G("item_emb.weight")
         gl = self.Wf("last_layernorm.weight")
         fused = ops.sas_block_fused_ok(d, dt)
+        fork = self.side.mark() if table_grad is not None and fused and "side" in s else None
         dx = g("ce_dx", (M, d), dt)
         if c["rows_fused"]:
             nb = ops.sas_ce_rows_nparts(M)
@@ -874,8 +781,11 @@ class SASEngine:
             ops.layernorm_bwd(s["xL"], df, gl, c["mu"], c["rs"], LN_EPS, dx, G("last_layernorm.weight"),
                               G("last_layernorm.bias"), wln, 0)
             segs = []
-        if after_rows is not None:
-            after_rows()
+        if fork is not None:
+            with self.side.run(after=fork, end=False):
+                table_grad()
+        elif table_grad is not None:
+            table_grad()
         if not fused:
             by_index = dt == torch.float32 or d in (64, 128, 256)
             self._backward_blocks_unfused(s, dx, grad, by_index, [ids], None, None, None)
@@ -889,159 +799,6 @@ class SASEngine:
         self._backward_blocks_fused(s, dx, grad, segs, tail=item_grads,
                                     pos=lambda dx: (ids, T, dx, p, self.salt["emb"], sb, G("pos_emb.weight")))
         self.side.join()
-
-    # ---- sampled softmax over batch-shared candidates (sas_sce.hip) ----------------------------
-    def _sce_cand(self, cand):
-        cand = cand.reshape(-1).contiguous()
-        K, kmax = cand.numel(), ops.sas_sce_max_k()
-        if K < 1 or K > kmax:
-            raise ValueError(f"the sampled-softmax head takes 1 .. {kmax} shared candidates, got {K}")
-        return cand
-
-    def sce_forward(self, ids, pos, cand, training, loss_out, max_labelled=None, clone_seed=True, logq=None):
-        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and the softmax cross-entropy of
-        the positive against the K candidates `cand` (int64 [K], shared by every row; id 0 and a row's own positive
-        are masked; SAS.sampled_ce_loss has the definition).  loss_out = {loss sum, valid count, mean}.  Returns the
-        saved state for sce_backward.  The sce_* buffers are sized by (cap, K, d) alone; nothing here allocates per
-        step or reads the host.  logq (fp32 [V + 1], device): the proposal's correction, subtracted from every logit
-        by the rs_sce_head_logq_* entries (no bias); sce_backward reads it from the saved state."""
-        d, dt = self.d, self.dt
-        if dt == torch.bfloat16 and d % 8:
-            raise ValueError(f"the bf16 sampled-softmax head needs hidden units divisible by 8 (got {d}); "
-                             "use fp32 mode (rs_dtype='fp32') at this width")
-        if not ops.sas_sce_ok(d, dt):
-            raise ValueError(f"the sampled-softmax head covers hidden units up to 1024 (got {d})")
-        cand = self._sce_cand(cand)
-        E = self.W("item_emb.weight")
-        logq = check_logq(logq, E)
-        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
-        c = self._valid_rows_forward(s, pos, max_labelled)
-        ws = self.ws.get("sce_ws", (ops.sas_sce_ws_numel(c["cap"], cand.numel(), d),), torch.float32)
-        if logq is None:
-            ops.sas_sce_fwd(c["hl"], c["lab"], c["cnt"], c["cap"], E, cand, c["div"], ws, loss_out)
-        else:                                           # the same workspace: rs_sce_head_ws_bytes without a bias
-            ops.sce_head_fwd(c["hl"], c["lab"], c["cnt"], c["cap"], E, None, cand, c["div"], ws, loss_out, logq=logq)
-        c.update(cand=cand, sce_ws=ws, logq=logq)
-        s.update(ce=c)
-        return s
-
-    def sce_backward(self, s, grad, dloss=None):
-        """Accumulates every parameter gradient of sce_forward's loss (times *dloss, a device scalar, if given) into
-        the flat fp32 buffer ``grad``.  The head's part of the item table's gradient -- coef_r f_r at row pos_r and
-        dEc[j] at row cand_j -- goes through an inverted index of its own (rs_item_index_build over the cap + K keys,
-        rs_item_grad_f32: one writer per table row, duplicates summed in sorted-entry order), on the side stream
-        beside the blocks' backward (fused path; else on the main stream); the lookup part follows on that same
-        stream after the blocks' backward, as in ce_backward: one writer at a time, fixed order, no float atomics."""
-        c = s["ce"]
-        d = self.d
-        f32 = torch.float32
-        g = self.ws.get
-        cap, cnt, hl, lab, cand = c["cap"], c["cnt"], c["hl"], c["lab"], c["cand"]
-        K = cand.numel()
-        GE = self.flat.view("item_emb.weight", grad)
-        sk = ops.sas_sce_dh_splits(cap, K, d)          # one fp32 slab per split of the candidates
-        dh, coef = g("sce_dh", (sk, cap, d), f32), g("sce_coef", (cap,), f32)
-        src, keys = g("sce_src", (cap + K, d), f32), g("sce_keys", (cap + K,), torch.int64)
-        if c["logq"] is None:
-            ops.sas_sce_bwd(hl, lab, cnt, cap, self.W("item_emb.weight"), cand, c["div"], dloss, c["sce_ws"], dh, coef,
-                            src[:cap], src[cap:], keys)
-        else:
-            ops.sce_head_bwd(hl, lab, cnt, cap, self.W("item_emb.weight"), None, cand, c["div"], dloss, c["sce_ws"],
-                             dh, coef, src[:cap], src[cap:], None, keys, logq=c["logq"])
-        # the index's key range: at least past the counting sort's table limit, so that the radix path is taken and
-        # the workspace is sized by the entry count alone (the counting sort's histograms are sized by the table)
-        rows = max(GE.shape[0], SCE_INDEX_ROWS)
-        iws = g("sce_itemidx", (ops.item_index_ws_bytes(1, cap + K, rows, d),), torch.uint8)
-
-        def head_table_grad():
-            ops.item_index_build([keys], rows, d, iws)
-            ops.item_grad(iws, 1, cap + K, src, 1.0, 0.0, 0, s["sb"], None, None, None, GE, table_rows=rows)
-        after_rows = head_table_grad
-        if ops.sas_block_fused_ok(d, self.dt) and "side" in s:
-            # the fused path: these launches depend on the head alone, so they run on the side branch beside the
-            # LayerNorm and blocks' backward; the lookup part continues that branch later and the step joins it once
-            # (SideBranch, rules 2 and 3)
-            fork = self.side.mark()
-
-            def after_rows():
-                with self.side.run(after=fork, end=False):
-                    head_table_grad()
-        self._valid_rows_backward(s, grad, dh, sk, after_rows=after_rows)
-
-    # ---- N negatives per position: multi-negative BCE / gBCE (sas_gbce.hip) ---------------------
-    def gbce_forward(self, ids, pos, neg, beta, training, loss_out, max_labelled=None, clone_seed=True):
-        """Blocks' forward, then on the rows with pos != 0 only: the last LayerNorm and the BCE of the positive
-        (weighted by beta) and the row's own N negatives neg[b, t, :] (int64 (B, T, N), or (B, T) as N = 1; read in
-        place through the compaction's source-row index; SAS.gbce_loss has the definition).  loss_out = {loss sum,
-        valid count, mean, negative-term sum}.  Returns the saved state for gbce_backward.  The gbce_* buffers are
-        sized by (cap, N, d) alone; nothing here allocates per step or reads the host."""
-        d, dt = self.d, self.dt
-        if dt == torch.bfloat16 and d % 8:
-            raise ValueError(f"the bf16 gBCE head needs hidden units divisible by 8 (got {d}); "
-                             "use fp32 mode (rs_dtype='fp32') at this width")
-        if not ops.sas_gbce_ok(d, dt):
-            raise ValueError(f"the gBCE head covers hidden units up to 1024 (got {d})")
-        B, T = ids.shape
-        if neg.dim() == 2:
-            neg = neg.unsqueeze(-1)
-        if neg.dim() != 3 or tuple(neg.shape[:2]) != (B, T):
-            raise ValueError(f"neg must be (B, T, N) or (B, T) = {(B, T)}, got {tuple(neg.shape)}")
-        N, nmax = neg.shape[2], ops.sas_gbce_max_n()
-        if N < 1 or N > nmax:
-            raise ValueError(f"the gBCE head takes 1 .. {nmax} negatives per position, got {N}")
-        neg = neg if neg.is_contiguous() else neg.contiguous()
-        _, _, s = self.forward(ids, pos, None, training, need_logits=False, clone_seed=clone_seed, ce=True)
-        c = self._valid_rows_forward(s, pos, max_labelled)
-        cap = c["cap"]
-        if cap * (1 + N) >= 2 ** 31:
-            raise ValueError(f"the gBCE head needs rows * (1 + N) < 2^31 (got {cap} rows, N = {N})")
-        # the compaction's source rows (rs_compact_rows' idx, which _valid_rows_forward filled); the dense fp32 form
-        # runs on all rows: identity
-        idx = None if c["dense"] else self.ws.get("ce_idx", (cap,), torch.int32)
-        ws = self.ws.get("gbce_ws", (ops.sas_gbce_ws_numel(cap, N, d),), torch.float32)
-        ops.sas_gbce_fwd(c["hl"], c["lab"], idx, c["cnt"], cap, self.W("item_emb.weight"), neg, N, beta, c["div"], ws,
-                         loss_out)
-        c.update(neg=neg, N=N, beta=float(beta), idx=idx, gbce_ws=ws)
-        s.update(ce=c)
-        return s
-
-    def gbce_backward(self, s, grad, dloss=None):
-        """Accumulates every parameter gradient of gbce_forward's loss (times *dloss, a device scalar, if given) into
-        the flat fp32 buffer ``grad``.  The head's part of the item table's gradient -- g_rj f_r at rows pos_r and
-        neg_rj -- goes through an inverted index of its own over the cap * (1 + N) head entries (rs_item_index_build,
-        rs_item_grad_weighted: one writer per table row, no [entries][d] buffer), on the side branch beside the blocks'
-        backward (fused path; else on the main stream); the lookup part follows on that branch after the blocks'
-        backward, as in sce_backward: one writer at a time, fixed order, no float atomics."""
-        c = s["ce"]
-        d = self.d
-        f32 = torch.float32
-        g = self.ws.get
-        cap, N, hl = c["cap"], c["N"], c["hl"]
-        n = cap * (1 + N)
-        GE = self.flat.view("item_emb.weight", grad)
-        dh, w = g("gbce_dh", (1, cap, d), f32), g("gbce_w", (n,), f32)
-        keys = g("gbce_keys", (n,), torch.int64)
-        ops.sas_gbce_bwd(hl, c["lab"], c["idx"], c["cnt"], cap, self.W("item_emb.weight"), c["neg"], N, c["beta"],
-                         c["div"], dloss, c["gbce_ws"], dh, w, keys)
-        # the index's key range: past the counting sort's table limit, so that the workspace is sized by the entry
-        # count alone (as sce_backward)
-        rows = max(GE.shape[0], SCE_INDEX_ROWS)
-        iws = g("gbce_itemidx", (ops.item_index_ws_bytes(1, n, rows, d),), torch.uint8)
-
-        def head_table_grad():
-            ops.item_index_build([keys], rows, d, iws)
-            ops.item_grad_weighted(iws, cap, 1 + N, hl, w, GE, table_rows=rows)
-        after_rows = head_table_grad
-        if ops.sas_block_fused_ok(d, self.dt) and "side" in s:
-            # the fused path: these launches depend on the head alone, so they run on the side branch beside the
-            # LayerNorm and blocks' backward; the lookup part continues that branch later and the step joins it once
-            # (SideBranch, rules 2 and 3)
-            fork = self.side.mark()
-
-            def after_rows():
-                with self.side.run(after=fork, end=False):
-                    head_table_grad()
-        self._valid_rows_backward(s, grad, dh, 1, after_rows=after_rows)
 
     def enable_row_marks(self, min_rows=0):
         """Stamp the rows the inverted-index gradient writes (rs_item_grad_marked) so the optimizer can skip the

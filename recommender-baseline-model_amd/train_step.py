@@ -30,6 +30,7 @@ import torch
 from . import dp as dpx
 from . import ops
 from .engine_util import SideBranch, release_capture_events
+from .models.sas_model.heads import HEADS, GBCEHead
 from .optim import FusedAdam, FusedSGD, FusedStepLR, plan  # noqa: F401 (the optimizers stay importable from here)
 
 
@@ -205,20 +206,16 @@ class FusedTrainStep:
         self.optimizer, self.momentum, shard_rows, loss, self.max_grad_norm, self.dp = self._check_args(
             weight_decay, dp, vocab_shard, shard_rows, loss, logq, table_optim, optimizer, momentum, max_grad_norm)
         self.loss, self.table_optim, self._logq_arg = loss, table_optim, logq
+        # the row head of a SAS step's tied loss (models/sas_model/heads.py); None: bce, and BERT
+        self.head = None
         self.gbce_negs = self.gbce_beta = None
         if loss == "gbce":
-            from .models.sas_model.sas import gbce_beta as _gbce_beta
-            self.gbce_negs = int(getattr(model.sas, "sas_negs", 0) or 0)
-            if self.gbce_negs < 1:
-                raise ValueError("FusedTrainStep(loss='gbce') needs the model's args.sas_negs = N >= 1")
-            if gbce_beta is None:
-                gbce_beta = _gbce_beta(self.gbce_negs, model.sas.item_num, getattr(model.sas, "sas_gbce_t", 0.0))
-            if isinstance(gbce_beta, bool) or not isinstance(gbce_beta, (int, float)) or \
-                    not math.isfinite(gbce_beta) or gbce_beta < 0:
-                raise ValueError(f"gbce_beta must be a finite number >= 0, got {gbce_beta!r}")
-            self.gbce_beta = float(gbce_beta)
+            self.head = GBCEHead.for_step(model.sas, gbce_beta)
+            self.gbce_negs, self.gbce_beta = self.head.negs, self.head.beta
         elif gbce_beta is not None:
             raise ValueError(f"gbce_beta needs loss='gbce' (got loss={loss!r})")
+        elif self.kind == "sas" and loss in HEADS:
+            self.head = HEADS[loss]()
         self.logq = logq if isinstance(logq, torch.Tensor) else None
         self.engine = model.sas.engine() if self.kind == "sas" else model.engine()
         if self.kind == "bert":
@@ -337,7 +334,7 @@ class FusedTrainStep:
         # gradient is sparse again, but its head rows come from the fp32 index launch, which stamps nothing: off too.
         # (SAS: its head rows land in the marked table itself.  BERT's sampled head writes out.weight / out.bias, not the
         # marked token table, whose rows still come from the stamping launch alone: the marks stay on.)
-        tied_head = self.kind == "sas" and self.loss in ("ce", "sampled_ce", "gbce")
+        tied_head = self.head is not None
         # A sparse table takes no marks either: its untouched rows are not swept at all.
         sparse = table_optim == "sparse"
         no_marks = tied_head or sparse or self.optimizer == "sgd"       # (the marked sweeps are Adam's)
@@ -494,20 +491,10 @@ class FusedTrainStep:
                 if action is None:
                     write_aux()
                 split(tag, action)
-        if self.kind == "sas" and self.loss == "ce":
-            seq, pos = batch[0], batch[1]
-            saved = eng.ce_forward(seq, pos, True, self.loss_out, max_labelled=self.max_labelled, clone_seed=False)
-            eng.ce_backward(saved, self.flat.grad)
-        elif self.kind == "sas" and self.loss == "sampled_ce":
-            seq, pos, cand = batch
-            saved = eng.sce_forward(seq, pos, cand, True, self.loss_out, max_labelled=self.max_labelled,
-                                    clone_seed=False, logq=self.logq)
-            eng.sce_backward(saved, self.flat.grad)
-        elif self.kind == "sas" and self.loss == "gbce":
-            seq, pos, neg = batch
-            saved = eng.gbce_forward(seq, pos, self._gbce_neg(seq, neg), self.gbce_beta, True, self.loss_out,
-                                     max_labelled=self.max_labelled, clone_seed=False)
-            eng.gbce_backward(saved, self.flat.grad)
+        if self.head is not None:
+            saved = eng.rows_forward(self.head, batch[0], batch[1], self.head.extras(batch, self.logq), True,
+                                     self.loss_out, max_labelled=self.max_labelled, clone_seed=False)
+            eng.rows_backward(saved, self.flat.grad)
         elif self.kind == "sas":
             seq, pos, neg = batch
             pl, nl, saved = eng.forward(seq, pos, neg, True, clone_seed=False, fuse_head=eng.fused_head,
@@ -698,16 +685,6 @@ class FusedTrainStep:
             self.opt.step_keep_early(rng, max_wg=self.EARLY_HEAD_ADAM_WG)
         self._early_forked = True
 
-    def _gbce_neg(self, seq, neg):
-        """loss="gbce": the batch's neg as (B, T, N) with N = the model's sas_negs ((B, T) is N = 1)."""
-        if neg is None or neg.dim() not in (2, 3) or tuple(neg.shape[:2]) != tuple(seq.shape):
-            raise ValueError(f"loss='gbce' needs neg of shape (B, T, N) with (B, T) = {tuple(seq.shape)}")
-        n = 1 if neg.dim() == 2 else neg.shape[2]
-        if n != self.gbce_negs:
-            raise ValueError(f"loss='gbce': the batch has {n} negs per position, the model's sas_negs is "
-                             f"{self.gbce_negs}")
-        return neg
-
     def _batch(self, batch):
         """loss="ce": neg is ignored and may be None -- pos stands in, so the (seq, pos, neg) buffers keep their form."""
         if self.loss == "ce" and (len(batch) == 2 or batch[2] is None):
@@ -869,12 +846,11 @@ class FusedTrainStep:
         S = int(steps_per_graph)
         if S < 1:
             raise ValueError("steps_per_graph must be >= 1")
-        if S > 1 and self.loss == "sampled_ce":
+        if S > 1 and self.kind == "bert" and self.loss == "sampled_ce":
             raise ValueError("loss='sampled_ce' needs steps_per_graph = 1: cand has another shape than seq / pos, "
                              "and the unrolled graph takes one packed buffer")
-        if S > 1 and self.loss == "gbce":
-            raise ValueError("loss='gbce' needs steps_per_graph = 1: neg has another shape than seq / pos, and the "
-                             "unrolled graph takes one packed buffer")
+        if S > 1 and self.head is not None and not self.head.packs_with_seq:
+            raise ValueError(self.head.unroll_refusal)
         if S > 1 and self.dp and not self.graph_collectives:
             raise ValueError("steps_per_graph > 1 under DP needs the all-reduce inside the graph (graph_collectives)")
         self.steps_per_graph = S
@@ -1121,21 +1097,18 @@ class FusedTrainStep:
         S = self._unroll_check(steps_per_graph)
         self.sampler = sampler
         shape = (sampler.batch_size, sampler.max_len)
-        if self.loss == "gbce":
-            # no packed buffer: neg has another shape (replay_packed then goes through replay())
-            self.packed = None
-            self.static = [torch.zeros(n, dtype=torch.int64, device=self.flat.device)
-                           for n in (shape, shape, shape + (self.gbce_negs,))]
-        elif self.loss == "sampled_ce":
-            K = getattr(sampler, "shared_negs", None)
-            if not K:
-                raise ValueError("loss='sampled_ce' needs a sampler with shared_negs=K")
-            if self._logq_arg is None and getattr(sampler, "proposal", None) is not None:
+        third = None                  # the third tensor's shape where it is not seq's
+        if self.kind == "bert" and self.loss == "sampled_ce":
+            third = (sampler.shared_negs,)
+        elif self.head is not None and not self.head.packs_with_seq:
+            third = self.head.third_shape(shape, sampler)
+        if third is not None:
+            if self.loss == "sampled_ce" and self._logq_arg is None and getattr(sampler, "proposal", None) is not None:
                 self.logq = sampler.proposal.logq          # the candidates come from it: the loss corrects for it
-            # no packed buffer: cand has another shape (replay_packed then goes through replay(), as after capture()
-            # with inputs of different shapes)
+            # no packed buffer: the third tensor has another shape (replay_packed then goes through replay(), as after
+            # capture() with inputs of different shapes)
             self.packed = None
-            self.static = [torch.zeros(n, dtype=torch.int64, device=self.flat.device) for n in (shape, shape, (K,))]
+            self.static = [torch.zeros(n, dtype=torch.int64, device=self.flat.device) for n in (shape, shape, third)]
         else:
             self.packed = torch.zeros((want,) + shape, dtype=torch.int64, device=self.flat.device)
             self.static = list(self.packed.unbind(0))

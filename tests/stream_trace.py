@@ -12,7 +12,8 @@ Streams are labelled s0, s1, ... and events numbered 0, 1, ... in order of first
 stream's identity is its handle, an event's the object.  ``wait_stream`` is one entry (torch forms it from an event of
 its own, which is not listed).  Only torch's own primitives and ``ops.call`` are patched, so the recorder runs on any
 revision of the package; tests/golden/step_traces.json holds the traces of the revision before the side-branch helper
-(the optimizer variants at the end of CASES: of the revision before the optimizers moved into rbm_amd.optim).
+(the optimizer variants in CASES: of the revision before the optimizers moved into rbm_amd.optim; the row-head cases at
+the end of CASES: of the revision before the row-head protocol, rbm_amd.models.sas_model.heads).
 """
 import argparse
 
@@ -81,24 +82,31 @@ def streams(trace):
 
 
 # ------------------------------------------------------------------ the cases
-def _sas(d, dtype, loss, turnaround="1", K=0, **step_kw):
+def _sas(d, dtype, loss, turnaround="1", K=0, N=0, ce_rows=None, logq=False, **step_kw):
     def make(monkeypatch):
         import rbm_amd.data as synth
         from rbm_amd.models import model_factory
         from rbm_amd.train_step import FusedTrainStep
         monkeypatch.setenv("RS_SAS_TURNAROUND_FUSE", turnaround)
+        if ce_rows is not None:
+            monkeypatch.setenv("RS_SAS_CE_ROWS", ce_rows)
         V, T, B = 200, 16, 4
         torch.manual_seed(0)
         a = argparse.Namespace(model_code="sas", num_items=V, max_len=T, device="cuda", sas_hidden_units=d,
                                sas_num_blocks=2, sas_heads=1, sas_dropout=0.2, l2_emb=0.0, rs_dtype=dtype,
-                               sas_loss=loss, sas_shared_negs=K)
-        tr = FusedTrainStep(model_factory(a), lr=1e-3, **step_kw)
+                               sas_loss=loss, sas_shared_negs=K, sas_negs=N)
+        kw = dict(step_kw)
+        if logq:        # a normalised proposal over the V + 1 rows (entry 0 is never read)
+            kw["logq"] = torch.log_softmax(torch.arange(V + 1, dtype=torch.float32), 0).cuda()
+        tr = FusedTrainStep(model_factory(a), lr=1e-3, **kw)
         rng = np.random.default_rng(7)
         batches = []
         for _ in range(2):
             seq, pos, neg = (torch.from_numpy(x).cuda() for x in synth.sas_batch(rng, B, T, V))
             if loss == "sampled_ce":
                 neg = torch.from_numpy(rng.integers(1, V + 1, K)).cuda()
+            if loss == "gbce":
+                neg = torch.from_numpy(rng.integers(1, V + 1, (B, T, N))).cuda()
             batches.append((seq, pos, neg))
         return tr, batches
     return make
@@ -145,6 +153,14 @@ CASES = {
     "sas_bce_clip": _sas(64, "bf16", "bce", max_grad_norm=1.0),
     "bert_sampled_ce_sparse_clip": _bert(300, 24, 64, 1, 2, 8, loss="sampled_ce", K=50, table_optim="sparse",
                                          max_grad_norm=1.0),
+    # the row heads' other forms (recorded at the revision before the row-head protocol, models/sas_model/heads.py)
+    "sas_gbce": _sas(64, "bf16", "gbce", N=3),
+    "sas_gbce_sparse_tables": _sas(64, "bf16", "gbce", N=3, table_optim="sparse"),
+    "sas_sampled_ce_logq": _sas(64, "bf16", "sampled_ce", K=16, logq=True),
+    "sas_ce_composed_rows": _sas(64, "bf16", "ce", ce_rows="0"),
+    "sas_fp32_ce": _sas(50, "fp32", "ce"),
+    "sas_fp32_sampled_ce": _sas(64, "fp32", "sampled_ce", K=16),
+    "sas_fp32_gbce": _sas(50, "fp32", "gbce", N=2),
 }
 
 

@@ -2,7 +2,8 @@
 branches fork and join), pinned as a trace: two consecutive eager steps of each case of tests/stream_trace.py -- the
 first takes the `_wT is None` / `_side_refreshed` path, the second the optimizer-written transposes -- must issue
 exactly the launches, event records and waits stored in tests/golden/step_traces.json, which the revision before the
-helper produced.  And engine_util.new_stream: distinct streams at every offset of torch's round-robin pool."""
+helper produced (the later cases: the revisions named in stream_trace's docstring).  And engine_util.new_stream:
+distinct streams at every offset of torch's round-robin pool."""
 import json
 import os
 
@@ -29,8 +30,10 @@ def test_step_trace_equals_the_stored_one(name, monkeypatch):
         for i, (g, e) in enumerate(zip(got, exp)):
             assert g == e, f"step {k}, entry {i}: {g} != {e}"
         assert len(got) == len(exp), f"step {k}: {len(got)} entries, stored {len(exp)}"
-    if name == "sas_fp32_bce":
-        assert all(stream_trace.streams(t) == {"s0"} for t in traces)          # the unfused path: one stream
+    if name in ("sas_fp32_bce", "sas_fp32_ce", "sas_fp32_gbce", "sas_fp32_sampled_ce"):
+        # the unfused path: one stream (sas_fp32_sampled_ce too -- the revision before the row-head protocol recorded
+        # its head table gradient on the main stream, after the LayerNorm backward)
+        assert all(stream_trace.streams(t) == {"s0"} for t in traces)
     if name == "bert_big_vocab":
         # the early head and token-table Adam updates run on the optimizer's branch: a third stream
         assert tr._early_ok and tr.engine.overwritten_grads() is not None

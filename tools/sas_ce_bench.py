@@ -28,6 +28,7 @@ import rbm_amd  # noqa: E402,F401
 import rbm_amd.data as synth  # noqa: E402
 from rbm_amd import ops  # noqa: E402
 from rbm_amd.models import model_factory  # noqa: E402
+from rbm_amd.models.sas_model.heads import CEHead  # noqa: E402
 from rbm_amd.models.sas_model.sas import LN_EPS  # noqa: E402
 from rbm_amd.train_step import FusedTrainStep  # noqa: E402
 
@@ -84,8 +85,8 @@ def head_launches(cfg, batch, reps):
     out = torch.zeros(4, device="cuda")
     grad = torch.zeros(eng.flat.numel, device="cuda")
     seq, pos = batch[0], batch[1]
-    s = eng.ce_forward(seq, pos, True, out)
-    eng.ce_backward(s, grad)
+    s = eng.rows_forward(CEHead(), seq, pos, (), True, out)
+    eng.rows_backward(s, grad)
     torch.cuda.synchronize()
     c, g = s["ce"], eng.ws.get
     M, d, cap, V1 = seq.numel(), eng.d, c["cap"], c["V1"]
@@ -94,11 +95,8 @@ def head_launches(cfg, batch, reps):
     E, gl, bl = eng.W("item_emb.weight"), eng.Wf("last_layernorm.weight"), eng.Wf("last_layernorm.bias")
     idx, rank, cnt, hl, lab, div = g("ce_idx", (cap,), torch.int32), c["rank"], c["cnt"], c["hl"], c["lab"], c["div"]
     mu, rs, wce = c["mu"], c["rs"], c["wce"]
-    dl = g("ce_dlogits", (cap, c["V1p"]), bf)[:, :V1]
+    dl, slab, sk, slab_d = c["dlogits"], c["slab_dE"], c["dh_splits"], c["slab_dh"]
     GE = eng.flat.view("item_emb.weight", grad)
-    slab = g("ce_slab_dE", (ops.wgrad_slab_numel(cap, V1, d),), f32)
-    sk = int(max(1, min(64, -(-V1 // 2048))))
-    slab_d = g("ce_slab_dh", (sk * cap * d,), f32)
     dx, part = g("ce_dx", (M, d), bf), g("ce_lnp", (2 * d * ops.sas_ce_rows_nparts(M),), f32)
     f, mu_f, rs_f = torch.empty(M, d, dtype=bf, device="cuda"), torch.empty(M, device="cuda"), torch.empty(M, device="cuda")
     df, wln = torch.empty(M, d, dtype=bf, device="cuda"), torch.empty(2 * 512 * d, device="cuda")

@@ -34,7 +34,7 @@ import rbm_amd  # noqa: E402,F401
 import rbm_amd.data as synth  # noqa: E402
 from rbm_amd import ops  # noqa: E402
 from rbm_amd.models import model_factory  # noqa: E402
-from rbm_amd.models.sas_model.sas import SCE_INDEX_ROWS  # noqa: E402
+from rbm_amd.models.sas_model.heads import GBCEHead  # noqa: E402
 from rbm_amd.train_step import FusedTrainStep  # noqa: E402
 from sas_ce_bench import CONFIGS, launch_us, model, replay_us  # noqa: E402
 
@@ -59,14 +59,13 @@ def head_launches(cfg, batch, neg, reps):
     eng.sync_compute_weights()
     out = torch.zeros(4, device="cuda")
     grad = torch.zeros(eng.flat.numel, device="cuda")
-    s = eng.gbce_forward(batch[0], batch[1], neg, 1.0, True, out)
-    eng.gbce_backward(s, grad)
+    s = eng.rows_forward(GBCEHead(1.0), batch[0], batch[1], (neg,), True, out)
+    eng.rows_backward(s, grad)
     torch.cuda.synchronize()
-    c, b = s["ce"], eng.ws.bufs
+    c = s["ce"]
     cap, d = c["cap"], eng.d
     E, GE = eng.W("item_emb.weight"), eng.flat.view("item_emb.weight", grad)
-    keys, w, iws = b["gbce_keys"], b["gbce_w"], b["gbce_itemidx"]
-    rows = max(GE.shape[0], SCE_INDEX_ROWS)
+    keys, w, iws, rows = c["keys"], c["w"], c["iws"], c["index_rows"]
     n = int(c["cnt"].item())
 
     def table():
@@ -76,7 +75,7 @@ def head_launches(cfg, batch, neg, reps):
     r["gbce_fwd_us"] = launch_us(lambda: ops.sas_gbce_fwd(c["hl"], c["lab"], c["idx"], c["cnt"], cap, E, neg, N, 1.0,
                                                           c["div"], c["gbce_ws"], out), reps)
     r["gbce_bwd_us"] = launch_us(lambda: ops.sas_gbce_bwd(c["hl"], c["lab"], c["idx"], c["cnt"], cap, E, neg, N, 1.0,
-                                                          c["div"], None, c["gbce_ws"], b["gbce_dh"], w, keys), reps)
+                                                          c["div"], None, c["gbce_ws"], c["dh"], w, keys), reps)
     r["gbce_table_grad_us"] = launch_us(table, reps)
     r["gbce_head_us"] = round(r["gbce_fwd_us"] + r["gbce_bwd_us"] + r["gbce_table_grad_us"], 2)
     # bytes from the shapes: the table rows gathered (bf16), the ids read, the row itself, the per-entry outputs
@@ -88,7 +87,7 @@ def head_launches(cfg, batch, neg, reps):
     r["gbce_bwd_TBps"] = round(bwd / r["gbce_bwd_us"] / 1e6, 3)
     r["gbce_fwd_over_hbm_peak"] = round(fwd / (r["gbce_fwd_us"] * 1e-6) / HBM_PEAK, 3)
     r["gbce_bwd_over_hbm_peak"] = round(bwd / (r["gbce_bwd_us"] * 1e-6) / HBM_PEAK, 3)
-    r["gbce_bytes"] = sum(v.numel() * v.element_size() for k, v in b.items() if k.startswith("gbce_"))
+    r["gbce_bytes"] = sum(c[k].numel() * c[k].element_size() for k in ("gbce_ws", "dh", "w", "keys", "iws"))
     return r
 
 

@@ -34,7 +34,7 @@ import rbm_amd  # noqa: E402,F401
 import rbm_amd.data as synth  # noqa: E402
 from rbm_amd import ops  # noqa: E402
 from rbm_amd.dataloaders import ItemProposal  # noqa: E402
-from rbm_amd.models.sas_model.sas import SCE_INDEX_ROWS  # noqa: E402
+from rbm_amd.models.sas_model.heads import SampledCEHead  # noqa: E402
 from rbm_amd.train_step import FusedTrainStep  # noqa: E402
 from sas_ce_bench import CONFIGS, launch_us, model, replay_us  # noqa: E402
 
@@ -46,14 +46,13 @@ def head_launches(cfg, batch, cand, reps, proposal=None):
     eng.sync_compute_weights()
     out = torch.zeros(4, device="cuda")
     grad = torch.zeros(eng.flat.numel, device="cuda")
-    s = eng.sce_forward(batch[0], batch[1], cand, True, out)
-    eng.sce_backward(s, grad)
+    s = eng.rows_forward(SampledCEHead(), batch[0], batch[1], (cand,), True, out)
+    eng.rows_backward(s, grad)
     torch.cuda.synchronize()
-    c, b = s["ce"], eng.ws.bufs
+    c = s["ce"]
     cap, d, K = c["cap"], eng.d, cand.numel()
     E, GE = eng.W("item_emb.weight"), eng.flat.view("item_emb.weight", grad)
-    src, keys, iws = b["sce_src"], b["sce_keys"], b["sce_itemidx"]
-    rows = max(GE.shape[0], SCE_INDEX_ROWS)
+    src, keys, iws, rows = c["src"], c["keys"], c["iws"], c["index_rows"]
 
     def table():
         ops.item_index_build([keys], rows, d, iws)
@@ -62,7 +61,7 @@ def head_launches(cfg, batch, cand, reps, proposal=None):
     r["sce_fwd_us"] = launch_us(lambda: ops.sas_sce_fwd(c["hl"], c["lab"], c["cnt"], cap, E, cand, c["div"],
                                                         c["sce_ws"], out), reps)
     r["sce_bwd_us"] = launch_us(lambda: ops.sas_sce_bwd(c["hl"], c["lab"], c["cnt"], cap, E, cand, c["div"], None,
-                                                        c["sce_ws"], b["sce_dh"], b["sce_coef"], src[:cap], src[cap:],
+                                                        c["sce_ws"], c["dh"], c["coef"], src[:cap], src[cap:],
                                                         keys), reps)
     r["sce_table_grad_us"] = launch_us(table, reps)
     if proposal is not None:
@@ -70,14 +69,13 @@ def head_launches(cfg, batch, cand, reps, proposal=None):
         r["sce_logq_fwd_us"] = launch_us(lambda: ops.sce_head_fwd(c["hl"], c["lab"], c["cnt"], cap, E, None, cand,
                                                                   c["div"], c["sce_ws"], out, logq=q), reps)
         r["sce_logq_bwd_us"] = launch_us(lambda: ops.sce_head_bwd(c["hl"], c["lab"], c["cnt"], cap, E, None, cand,
-                                                                  c["div"], None, c["sce_ws"], b["sce_dh"],
-                                                                  b["sce_coef"], src[:cap], src[cap:], None, keys,
-                                                                  logq=q), reps)
+                                                                  c["div"], None, c["sce_ws"], c["dh"], c["coef"],
+                                                                  src[:cap], src[cap:], None, keys, logq=q), reps)
         draws = torch.empty_like(cand)
         r["alias_items_us"] = launch_us(lambda: ops.alias_items(sb, 7, proposal.table, draws), reps)
         r["uniform_items_us"] = launch_us(lambda: ops.uniform_items(sb, 7, proposal.item_num, draws), reps)
     r["sce_head_us"] = round(r["sce_fwd_us"] + r["sce_bwd_us"] + r["sce_table_grad_us"], 2)
-    r["sce_bytes"] = sum(v.numel() * v.element_size() for k, v in b.items() if k.startswith("sce_"))
+    r["sce_bytes"] = sum(c[k].numel() * c[k].element_size() for k in ("sce_ws", "dh", "coef", "src", "keys", "iws"))
     return r
 
 
